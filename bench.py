@@ -1,7 +1,7 @@
 """bench.py — batched HTTP L7 policy verdicts on the 10K-rule set (BASELINE
 config 5), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--requests-per-gpu B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--requests-per-gpu B] [--dump-outputs DIR] [--full]
 
 A step is one pass of the verdict kernel over the GPU's resident batch of B
 packed requests (default 125M = 1B / 8, so at N = 8 the node processes the
@@ -12,9 +12,12 @@ are all-reduced across ranks (RCCL) — the only collective on this path.  The
 10K rules are compiled once (rank 0) and every rank imports the same table
 image (cg_http_policy_export / _import).
 
-Rank 0 prints one JSON line with throughput, the roofline of the verdict
-kernel (HIP events on the kernel's stream), the same kernel on a 262K-distinct
-batch, the end-to-end raw path (config 5 as raw HTTP/1 heads resident in HBM
+Rank 0 prints one JSON line with throughput and the roofline of the verdict
+kernel (HIP events on the kernel's stream around the timed steps).  A plain
+run does no more than that: set-up, warm-up, the K timed steps, the outputs of
+the last one if --dump-outputs is given, the line.  With --full the line also
+holds the parity check of the resident batch against the oracle, the sustained
+rate, the same kernel on a 262K-distinct batch, the end-to-end raw path (config 5 as raw HTTP/1 heads resident in HBM
 → cg_http_verdicts_raw_dev: parse, pack and verdicts on the GPU), the host
 entry (the distinct requests as header lists in host memory →
 cg_http_verdicts_fields_host, PCIe-inclusive) and the CPU oracle (the Envoy-faithful std::regex rule scan) timed on a bounded sample on
@@ -48,6 +51,13 @@ def parse():
     ap.add_argument("--distinct", type=int, default=8_388_608)
     ap.add_argument("--small-distinct", type=int, default=262_144,
                     help="second measurement of the kernel on a batch with this many distinct requests (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the oracle parity check, the sustained rate, the "
+                         "262K-distinct batch, the end-to-end raw path, the host entry and the CPU baselines (the "
+                         "options that skip or size one of these legs apply to such a run)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the verdicts of the last one to DIR/<name>.npy (float32, "
+                         "request order; see dump_outputs)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end raw-heads measurement")
     ap.add_argument("--e2e-layout", default="device", choices=["host", "device"],
                     help="raw path sequence for end_to_end: device (the default: slots, chunk table and header "
@@ -98,6 +108,10 @@ def main():
         raise SystemExit(spawn_ranks(args.gpus))
     if args.cpu_rehearsal:
         return rehearse(args)
+    if not args.full:
+        # a plain run times the headline only; every other leg is --full's
+        args.no_check = args.no_e2e = args.no_cpu_baseline = True
+        args.small_distinct, args.sustain_seconds = 0, 0.0
     import torch
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -165,10 +179,7 @@ def main():
         torch.cuda.synchronize()
         import oracle
         out_tiles = d_out.view(-1, 64)[torch.from_numpy(tile_map).to(dev)]
-        slots = out_tiles.reshape(-1).cpu().numpy()  # the first copy, in b's slot order
-        got = np.zeros(D, np.uint8)
-        real = b.order < D
-        got[b.order[real]] = slots[real]
+        got = request_order(out_tiles.reshape(-1).cpu().numpy(), b, D)  # the first copy
         exp = oracle.HttpOracle(pols).eval(**rq, nthreads=host_threads())
         check = bool(np.array_equal(got, exp))
         if not check:
@@ -191,6 +202,9 @@ def main():
     wall = t_end - t_start
     kernel_ms = sum(a.elapsed_time(z) for a, z in kev) / args.steps
     allreduce_ms = sum(a.elapsed_time(z) for a, z in aev) / args.steps if aev else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "" if world == 1 else f"_rank{rank}", d_out, b, tile_map, D,
+                     reps if args.layout == "tile" else 1, dev, torch)
     rank_wall = wall
     wall = max_over_ranks(wall, dist, dev, torch)
     sustained = None
@@ -284,6 +298,43 @@ def host_threads() -> int:
     """Host threads given to this GPU's process: OMP_NUM_THREADS (16 on the
     GPU box: its per-GPU CPU share), else the cores here up to 16."""
     return int(os.environ.get("OMP_NUM_THREADS", "0")) or min(16, os.cpu_count() or 1)
+
+
+def request_order(slots: np.ndarray, b, D: int) -> np.ndarray:
+    """Per-slot values of packed batch b (b's slot order, padding slots
+    included) as one value per request, in the order the requests were given
+    to the packer."""
+    got = np.zeros(D, slots.dtype)
+    real = b.order < D
+    got[b.order[real]] = slots[real]
+    return got
+
+
+DUMP_MAX = 5_000_000  # requests in verdicts.npy, twice as many in allowed_copies.npy: 60 MB of float32 at most
+
+
+def dump_outputs(path: str, tag: str, d_out, b, tile_map: np.ndarray, D: int, reps: int, dev, torch) -> None:
+    """--dump-outputs: what the last timed step left in d_out, the verdict
+    bytes a caller of http_verdicts_dev receives, as float32 per distinct
+    request in request order (the requests are seeded: the same arguments give
+    the same requests, whatever order the packer put them in):
+    verdicts.npy, the verdict of each request's first copy, and
+    allowed_copies.npy, how many of its `reps` copies were allowed (every
+    slot of the output is in that sum; tile layout, where a tile's copies lie
+    in a row: the caller passes reps = 1 otherwise).  Past DUMP_MAX distinct
+    requests the first, and past 2 * DUMP_MAX the second, holds a fixed,
+    seeded sample of them (the default 8M: all of them in the second)."""
+    os.makedirs(path, exist_ok=True)
+    tiles = d_out.view(-1, 64)
+    tm = torch.from_numpy(tile_map).to(dev)
+    first = tiles[tm]
+    copies = first.to(torch.float32)
+    for r in range(1, reps):
+        copies += tiles[tm + r]
+    for name, t, most in (("verdicts", first, DUMP_MAX), ("allowed_copies", copies, 2 * DUMP_MAX)):
+        keep = slice(None) if D <= most else np.sort(np.random.default_rng(0xD0).choice(D, most, replace=False))
+        a = request_order(t.reshape(-1).cpu().numpy(), b, D)[keep]
+        np.save(os.path.join(path, f"{name}{tag}.npy"), a.astype(np.float32))
 
 
 def max_over_ranks(sec: float, dist, dev, torch) -> float:

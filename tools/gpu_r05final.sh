@@ -14,7 +14,7 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu -v --timeout 200 --timeout-m
 rc=$?; echo "pytest rc=$rc" >> $out/rc.txt; fatal $rc
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc" >> $out/rc.txt; fatal $rc
-timeout -k 10 500 python3 bench.py > $out/bench.log 2>&1
+timeout -k 10 500 python3 bench.py --full > $out/bench.log 2>&1
 rc=$?; echo "bench rc=$rc" >> $out/rc.txt; fatal $rc
 bash tools/gpu_headline_prof.sh ${tag}_headline
 rc=$?; echo "headline rc=$rc" >> $out/rc.txt; fatal $rc

@@ -13,7 +13,7 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu -v --timeout 200 --timeout-m
 rc=$?; echo "pytest rc=$rc" >> $out/rc.txt; fatal $rc
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc" >> $out/rc.txt; fatal $rc
-timeout -k 10 500 python3 bench.py > $out/bench.log 2>&1
+timeout -k 10 500 python3 bench.py --full > $out/bench.log 2>&1
 rc=$?; echo "bench rc=$rc" >> $out/rc.txt; fatal $rc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/raw -o run --output-format csv -- python3 tools/bench_paths.py --paths httpraw,httpfields --steps 3 --cpu-seconds 0 > $out/raw.log 2>&1
 rc=$?; echo "raw rc=$rc" >> $out/rc.txt; fatal $rc

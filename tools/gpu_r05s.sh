@@ -24,5 +24,5 @@ for r in 1 2; do
 done
 bash tools/gpu_headline_prof.sh ${tag}_headline
 rc=$?; echo "headline rc=$rc" >> $out/rc.txt; fatal $rc
-timeout -k 10 500 python3 bench.py > $out/bench.log 2>&1
+timeout -k 10 500 python3 bench.py --full > $out/bench.log 2>&1
 rc=$?; echo "bench rc=$rc" >> $out/rc.txt; fatal $rc

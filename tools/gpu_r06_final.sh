@@ -16,9 +16,9 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu -v --timeout 200 --timeout-m
 rc=$?; echo "pytest rc=$rc" >> $out/rc.txt; fatal $rc
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc" >> $out/rc.txt; fatal $rc
-timeout -k 10 500 python3 bench.py > $out/bench.log 2>&1
+timeout -k 10 500 python3 bench.py --full > $out/bench.log 2>&1
 rc=$?; echo "bench rc=$rc" >> $out/rc.txt; fatal $rc
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $out/benchkt -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --sustain-seconds 0 --no-cpu-baseline > $out/bench_kt.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $out/benchkt -o run --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --sustain-seconds 0 --no-cpu-baseline > $out/bench_kt.log 2>&1
 rc=$?; echo "bench kt rc=$rc" >> $out/rc.txt; fatal $rc
 else
 timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $out/paths -o run --output-format csv -- python3 tools/bench_paths.py --paths l4,lpm,kafka,ipcache,l4ipc,proxylib,memcache,cassandra,kafkawire,kafkawirez,httpraw,httpfields --steps 5 --cpu-seconds 2 > $out/paths.jsonl 2> $out/paths.err
