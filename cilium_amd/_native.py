@@ -58,6 +58,8 @@ CG_KAFKA_TOPICS_IN_ARENA = 255
 CG_KAFKA_DECODE_OK, CG_KAFKA_DECODE_ERROR = 0, 1
 CG_KAFKA_V_DENY, CG_KAFKA_V_ALLOW, CG_KAFKA_V_CLOSE = 0, 1, 2
 
+CG_SEL_MATCH_LABEL, CG_SEL_IN, CG_SEL_NOT_IN, CG_SEL_EXISTS, CG_SEL_DOES_NOT_EXIST = 0, 1, 2, 3, 4
+
 
 class CiliumGPUError(RuntimeError):
     def __init__(self, code: int, msg: str):
@@ -82,6 +84,20 @@ class PolicyEntryC(C.Structure):
 
 class CidrC(C.Structure):
     _fields_ = [("family", C.c_uint8), ("prefixlen", C.c_uint8), ("pad", C.c_uint8 * 2), ("addr", C.c_uint8 * 16)]
+
+
+class SelectorTableC(C.Structure):
+    """cg_selector_table"""
+    _fields_ = [("n_selectors", C.c_size_t), ("req_off", C.c_void_p), ("ops", C.c_void_p),
+                ("key_blob", C.c_void_p), ("key_off", C.c_void_p), ("val_off", C.c_void_p),
+                ("val_blob", C.c_void_p), ("val_str_off", C.c_void_p)]
+
+
+class SelcacheRulesC(C.Structure):
+    """cg_selcache_rules"""
+    _fields_ = [("n_rules", C.c_size_t), ("subject", C.c_void_p), ("dir_flags", C.c_void_p),
+                ("req_off", C.c_void_p * 2), ("req_idx", C.c_void_p * 2),
+                ("allow_off", C.c_void_p * 2), ("allow_idx", C.c_void_p * 2)]
 
 
 # Exported symbols and their signatures: (restype, argtypes)
@@ -176,6 +192,17 @@ SIGNATURES = {
     "cg_diag_l4_eval_host": (C.c_int, [_u64, _u32, _p, _sz, _p]),
     "cg_diag_ipcache_eval_host": (C.c_int, [_u64, _u32, _p, _sz, _p, _p, _sz, _p]),
     "cg_diag_prefilter_eval_host": (C.c_int, [_u64, _u32, _p, _sz, _p, _p, _sz, _p]),
+    "cg_selcache_create": (C.c_int, [_u64, C.POINTER(_u32)]),
+    "cg_selcache_destroy": (C.c_int, [_u64, _u32]),
+    "cg_selcache_set_identities": (C.c_int, [_u64, _u32, _p, _sz, _p, _p, _p, _p, _p]),
+    "cg_selcache_set_rules": (C.c_int, [_u64, _u32, C.POINTER(SelectorTableC), C.POINTER(SelcacheRulesC)]),
+    "cg_selcache_info": (C.c_int, [_u64, _u32, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
+    "cg_selcache_match_dev": (C.c_int, [_u64, _u32, C.POINTER(SelectorTableC), _p, _sz, _p]),
+    "cg_selcache_match_host": (C.c_int, [_u64, _u32, C.POINTER(SelectorTableC), _p, _sz]),
+    "cg_selcache_reach_dev": (C.c_int, [_u64, _u32, _p, _sz, _p, _p, _p, _p]),
+    "cg_selcache_reach_host": (C.c_int, [_u64, _u32, _p, _sz, _p, _p, _p]),
+    "cg_diag_selcache_match_host": (C.c_int, [_u64, _u32, C.POINTER(SelectorTableC), _p, _sz, _u32]),
+    "cg_diag_selcache_reach_host": (C.c_int, [_u64, _u32, _p, _sz, _p, _p, _p, _u32]),
 }
 
 

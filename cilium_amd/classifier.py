@@ -97,6 +97,12 @@ class Classifier:
     def ipcache(self, max_entries: int = 0) -> "IPCache":
         return IPCache(self, max_entries)
 
+    # ------------------------------------------------- selector cache --
+    def selector_cache(self) -> "SelectorCache":
+        """Label selectors → identity sets and L3 reachability (selcache.py)."""
+        from .selcache import SelectorCache
+        return SelectorCache(self)
+
     # ----------------------------------------------------------- HTTP --
     def update_http_policy(self, policies: list[dict] | bytes | str) -> None:
         """Install NPDS NetworkPolicies (all-or-nothing)."""

@@ -23,6 +23,7 @@
 #include "lpm.h"
 #include "regex.h"
 #include "ring.h"
+#include "selcache.h"
 
 using namespace cg;
 
@@ -75,6 +76,12 @@ PolicyMapState& get_map(Engine& e, uint32_t id) {
 IpcacheState& get_ipc(Engine& e, uint32_t id) {
   auto it = e.ipcaches.find(id);
   if (it == e.ipcaches.end()) fail(CG_NOT_FOUND, "unknown ipcache id");
+  return *it->second;
+}
+
+SelcacheState& get_sc(Engine& e, uint32_t id) {
+  auto it = e.selcaches.find(id);
+  if (it == e.selcaches.end()) fail(CG_NOT_FOUND, "unknown selector cache id");
   return *it->second;
 }
 
@@ -179,6 +186,7 @@ void cg_close(uint64_t h) {
     e->maps.clear();
     e->prefilters.clear();
     e->ipcaches.clear();
+    e->selcaches.clear();
     e->http.reset();
     e->kafka.reset();
     (void)hipStreamDestroy((hipStream_t)e->stream);
@@ -793,6 +801,223 @@ int cg_diag_ipcache_eval_host(uint64_t h, uint32_t ipc_id, const uint32_t* v4, s
       }
       out6[i] = cg_remote_endpoint_info{(uint32_t)v, (uint32_t)(v >> 32)};
     }
+  });
+}
+
+// ------------------------------------------------------- selector cache ----
+// The published snapshot, copied under the handle lock and held for the call.
+static std::shared_ptr<ScPublished> sc_pub(Engine& e, uint32_t sc_id) {
+  std::lock_guard<std::mutex> lk(e.mu);
+  SelcacheState& s = get_sc(e, sc_id);
+  if (s.dirty || !s.pub) s.rebuild(e);
+  return s.pub;
+}
+
+// The selector table of a match call: the caller's, interned against the
+// snapshot's identities, or (sels == NULL) the rule set's.
+static const ScSelTab& sc_table_of(const ScPublished& p, const cg_selector_table* sels, ScSelTab* own) {
+  if (!sels) return p.seltab;
+  *own = sc_compile_selectors(*p.idents, sc_parse_selectors(*sels));
+  return *own;
+}
+
+static void sc_check_cap(const ScPublished& p, const ScSelTab& t, const void* bits, size_t cap_words) {
+  const size_t need = t.sels.size() * (size_t)p.idents->words;
+  if (need && !bits) fail(CG_INVALID_ARGUMENT, "selcache match: NULL bits");
+  if (cap_words < need) fail(CG_INVALID_ARGUMENT, "selcache match: bits holds fewer than S * W words");
+}
+
+int cg_selcache_create(uint64_t h, uint32_t* sc_id) {
+  return guarded([&] {
+    auto e = get(h);
+    if (!sc_id) fail(CG_INVALID_ARGUMENT, "sc_id is NULL");
+    std::lock_guard<std::mutex> lk(e->mu);
+    const uint32_t id = e->next_id++;
+    e->selcaches[id] = std::make_unique<SelcacheState>();
+    *sc_id = id;
+  });
+}
+
+int cg_selcache_destroy(uint64_t h, uint32_t sc_id) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    get_sc(*e, sc_id);
+    if (e->has_gpu()) dev_sync(*e, nullptr);
+    e->selcaches.erase(sc_id);
+  });
+}
+
+int cg_selcache_set_identities(uint64_t h, uint32_t sc_id, const uint32_t* ids, size_t n, const uint32_t* label_off,
+                               const uint8_t* key_blob, const uint64_t* key_off, const uint8_t* val_blob,
+                               const uint64_t* val_off) {
+  return guarded([&] {
+    auto e = get(h);
+    auto snap = sc_compile_identities(ids, n, label_off, key_blob, key_off, val_blob, val_off);
+    std::lock_guard<std::mutex> lk(e->mu);
+    SelcacheState& s = get_sc(*e, sc_id);
+    s.idents = std::move(snap);
+    s.dirty = true;
+  });
+}
+
+int cg_selcache_set_rules(uint64_t h, uint32_t sc_id, const cg_selector_table* sels, const cg_selcache_rules* rules) {
+  return guarded([&] {
+    auto e = get(h);
+    if (!sels || !rules) fail(CG_INVALID_ARGUMENT, "selcache rules: NULL tables");
+    auto src = sc_parse_rules(*sels, *rules);
+    std::lock_guard<std::mutex> lk(e->mu);
+    SelcacheState& s = get_sc(*e, sc_id);
+    s.rules = std::move(src);
+    s.dirty = true;
+  });
+}
+
+int cg_selcache_info(uint64_t h, uint32_t sc_id, size_t* n_identities, size_t* words, size_t* n_selectors,
+                     size_t* n_rules) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    SelcacheState& s = get_sc(*e, sc_id);
+    if (n_identities) *n_identities = s.idents->n;
+    if (words) *words = s.idents->words;
+    if (n_selectors) *n_selectors = s.rules->sels.size();
+    if (n_rules) *n_rules = s.rules->n;
+  });
+}
+
+// An ad-hoc selector table's device copy lives until the kernel reading it
+// has finished: its DevTables fence waits when the last holder lets go.
+static ScSelDev sc_upload_table(const ScSelTab& t, DevTables& tab) {
+  return ScSelDev{tab.add(t.sels), tab.add(t.reqs), tab.add(t.vals), (uint32_t)t.sels.size()};
+}
+
+int cg_selcache_match_dev(uint64_t h, uint32_t sc_id, const cg_selector_table* sels, uint64_t* d_bits,
+                          size_t cap_words, void* stream) {
+  return guarded([&] {
+    auto e = get(h);
+    e->require_gpu();
+    const auto p = sc_pub(*e, sc_id);
+    ScSelTab own;
+    const ScSelTab& t = sc_table_of(*p, sels, &own);
+    sc_check_cap(*p, t, d_bits, cap_words);
+    e->set_device();
+    void* st = stream_of(*e, stream);
+    auto tmp = std::make_shared<DevTables>();
+    const ScSelDev dT = sels ? sc_upload_table(t, *tmp) : p->dT;
+    check_launch(launch_selcache_match(p->dI, dT, (unsigned long long*)d_bits, st, e->cus),
+                 "selcache match kernel launch");
+    fence(p->tab, st);
+    if (sels) fence(tmp, st);
+  });
+}
+
+int cg_selcache_match_host(uint64_t h, uint32_t sc_id, const cg_selector_table* sels, uint64_t* bits,
+                           size_t cap_words) {
+  return guarded([&] {
+    auto e = get(h);
+    e->require_gpu();
+    const auto p = sc_pub(*e, sc_id);
+    ScSelTab own;
+    const ScSelTab& t = sc_table_of(*p, sels, &own);
+    sc_check_cap(*p, t, bits, cap_words);
+    const size_t need = t.sels.size() * (size_t)p->idents->words;
+    if (!need) return;
+    e->set_device();
+    DevTables tmp;
+    const ScSelDev dT = sels ? sc_upload_table(t, tmp) : p->dT;
+    DevMem out;
+    out.alloc(need * sizeof(uint64_t));
+    check_launch(launch_selcache_match(p->dI, dT, out.as<unsigned long long>(), e->stream, e->cus),
+                 "selcache match kernel launch");
+    fence(p->tab, e->stream);
+    dev_sync(*e, nullptr);
+    hip_check(hipMemcpy(bits, out.get(), need * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
+  });
+}
+
+int cg_selcache_reach_dev(uint64_t h, uint32_t sc_id, const uint32_t* d_endpoints, size_t n, uint64_t* d_ing,
+                          uint64_t* d_eg, uint8_t* d_flags, void* stream) {
+  return guarded([&] {
+    auto e = get(h);
+    e->require_gpu();
+    if (n && (!d_endpoints || !d_ing || !d_eg || !d_flags)) fail(CG_INVALID_ARGUMENT, "selcache reach: NULL arrays");
+    const auto p = sc_pub(*e, sc_id);
+    e->set_device();
+    void* st = stream_of(*e, stream);
+    check_launch(launch_selcache_reach(p->dR, p->idents->n, p->idents->words, d_endpoints, n,
+                                       (unsigned long long*)d_ing, (unsigned long long*)d_eg, d_flags, st),
+                 "selcache reach kernel launch");
+    fence(p->tab, st);
+  });
+}
+
+static void sc_check_endpoints(const ScPublished& p, const uint32_t* eps, size_t n, const void* ing, const void* eg,
+                               const void* flags) {
+  if (n && (!eps || !ing || !eg || !flags)) fail(CG_INVALID_ARGUMENT, "selcache reach: NULL arrays");
+  for (size_t i = 0; i < n; ++i)
+    if (eps[i] >= p.idents->n) fail(CG_INVALID_ARGUMENT, "selcache reach: endpoint index outside the identity table");
+}
+
+int cg_selcache_reach_host(uint64_t h, uint32_t sc_id, const uint32_t* endpoints, size_t n, uint64_t* ing,
+                           uint64_t* eg, uint8_t* flags) {
+  return guarded([&] {
+    auto e = get(h);
+    e->require_gpu();
+    const auto p = sc_pub(*e, sc_id);
+    sc_check_endpoints(*p, endpoints, n, ing, eg, flags);
+    if (!n) return;
+    e->set_device();
+    const size_t W = p->idents->words, row = n * W * sizeof(uint64_t);
+    DevMem d_ep, d_ing, d_eg, d_fl;
+    d_ep.upload(endpoints, n * sizeof(uint32_t));
+    d_ing.alloc(row);
+    d_eg.alloc(row);
+    d_fl.alloc(n);
+    check_launch(launch_selcache_reach(p->dR, p->idents->n, p->idents->words, d_ep.as<uint32_t>(), n,
+                                       d_ing.as<unsigned long long>(), d_eg.as<unsigned long long>(),
+                                       d_fl.as<uint8_t>(), e->stream),
+                 "selcache reach kernel launch");
+    fence(p->tab, e->stream);
+    dev_sync(*e, nullptr);
+    if (row) {
+      hip_check(hipMemcpy(ing, d_ing.get(), row, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+      hip_check(hipMemcpy(eg, d_eg.get(), row, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+    }
+    hip_check(hipMemcpy(flags, d_fl.get(), n, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+  });
+}
+
+// The compiled tables walked on the host, as the kernels walk them.
+int cg_diag_selcache_match_host(uint64_t h, uint32_t sc_id, const cg_selector_table* sels, uint64_t* bits,
+                                size_t cap_words, uint32_t threads) {
+  return guarded([&] {
+    auto e = get(h);
+    const auto p = sc_pub(*e, sc_id);
+    ScSelTab own;
+    const ScSelTab& t = sc_table_of(*p, sels, &own);
+    sc_check_cap(*p, t, bits, cap_words);
+    sc_match_host(p->idents->view(), t.view(), bits, threads);
+  });
+}
+
+int cg_diag_selcache_reach_host(uint64_t h, uint32_t sc_id, const uint32_t* endpoints, size_t n, uint64_t* ing,
+                                uint64_t* eg, uint8_t* flags, uint32_t threads) {
+  return guarded([&] {
+    auto e = get(h);
+    const auto p = sc_pub(*e, sc_id);
+    sc_check_endpoints(*p, endpoints, n, ing, eg, flags);
+    {
+      // the rule selectors' matrix on the host, once per snapshot
+      std::lock_guard<std::mutex> lk(e->mu);
+      const size_t need = p->seltab.sels.size() * (size_t)p->idents->words;
+      if (p->host_m.size() != need || !need) {
+        p->host_m.assign(std::max<size_t>(need, 1), 0);
+        sc_match_host(p->idents->view(), p->seltab.view(), p->host_m.data(), threads);
+        if (!need) p->host_m.resize(1);
+      }
+    }
+    sc_reach_host(p->host_rules(), p->idents->n, p->idents->words, endpoints, n, ing, eg, flags, threads);
   });
 }
 

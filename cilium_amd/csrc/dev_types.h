@@ -856,4 +856,97 @@ CG_HD inline uint64_t ipc_v6_search_value(const IpcacheDev& t, uint64_t hi, uint
   return t.runs6[4 * (size_t)ipc_v6_run(t, hi, lo, l, r) + 2];
 }
 
+// ------------------------------------------------------- selector cache ----
+// Label selectors over the identity cache (selcache.h, kernels_selcache.hip;
+// pkg/policy/api/selector.go:279-310, pkg/labels/array.go:90-131).  Key parts,
+// sources and values are interned to u32 ids in one id space shared by the
+// identities and the selectors; the source "any" is id kScAny.
+constexpr uint32_t kScAny = 0;
+constexpr uint32_t kScNoKey = 0xFFFFFFFFu;  // never an interned id: an absent label slot
+constexpr uint32_t kScAlways = 1u << 31;    // ScSel.nreq: the empty selector / matchLabels reserved:all
+
+struct ScLabel {  // one label of an identity, in the identity's given order
+  uint32_t key, src, val, pad;
+};
+struct ScReq {  // one requirement: the label `src:key` selects, an operator, a value set
+  uint32_t key, src;
+  uint32_t op_nv;  // CG_SEL_* | value count << 8
+  uint32_t vbeg;   // first value id in ScSelDev.vals
+};
+struct ScSel {
+  uint32_t rbeg;  // first requirement
+  uint32_t nreq;  // requirement count | kScAlways
+};
+static_assert(sizeof(ScLabel) == 16 && sizeof(ScReq) == 16 && sizeof(ScSel) == 8, "selector cache records");
+
+struct ScIdentDev {
+  const uint32_t* lab_off;  // n + 1
+  const ScLabel* labels;
+  uint32_t n;      // identities
+  uint32_t words;  // ceil(n / 64)
+};
+struct ScSelDev {
+  const ScSel* sels;
+  const ScReq* reqs;
+  const uint32_t* vals;
+  uint32_t n;  // selectors
+};
+// A rule set over the rows of its selector table's match matrix M[n_sel][words].
+// Direction 0 = ingress, 1 = egress: req = FromRequires / ToRequires of every
+// direction rule, allow = the source / destination selectors of the direction
+// rules without ToPorts (rule.go:352-440).
+struct ScRuleDev {
+  const uint32_t* subject;  // n: selector row of the rule's EndpointSelector
+  const uint8_t* flags;     // n: bit 0 has ingress rules, bit 1 has egress rules
+  const uint32_t* req_off[2];
+  const uint32_t* req_idx[2];
+  const uint32_t* allow_off[2];
+  const uint32_t* allow_idx[2];
+  const unsigned long long* M;
+  uint32_t n;  // rules
+};
+
+// LabelArray.Get's condition for one label (array.go:90-131): the key parts
+// agree and the sources agree or either is "any".
+CG_HD inline bool sc_label_hit(uint32_t lkey, uint32_t lsrc, uint32_t key, uint32_t src) {
+  return lkey == key && (src == kScAny || lsrc == src || lsrc == kScAny);
+}
+
+// One requirement given whether a label was selected and whether its value is
+// in the requirement's value set (`in` implies `found`).
+CG_HD inline bool sc_req_holds(uint32_t op, bool found, bool in) {
+  switch (op) {
+    case CG_SEL_MATCH_LABEL:
+    case CG_SEL_IN: return in;
+    case CG_SEL_NOT_IN: return !in;
+    case CG_SEL_EXISTS: return found;
+    default: return !found;  // CG_SEL_DOES_NOT_EXIST (the compiler admits no other operator)
+  }
+}
+
+// Selector s against identity i, label by label (the host walker; the kernel
+// does the same with the labels staged in registers).
+CG_HD inline bool sc_matches(const ScIdentDev& I, const ScSelDev& T, uint32_t s, uint32_t i) {
+  const ScSel h = T.sels[s];
+  if (h.nreq & kScAlways) return true;
+  const uint32_t lo = I.lab_off[i], hi = I.lab_off[i + 1];
+  for (uint32_t r = h.rbeg; r < h.rbeg + h.nreq; ++r) {
+    const ScReq q = T.reqs[r];
+    bool found = false, in = false;
+    uint32_t got = 0;
+    for (uint32_t j = lo; j < hi; ++j) {
+      const ScLabel L = I.labels[j];
+      if (sc_label_hit(L.key, L.src, q.key, q.src)) {  // the first such label wins
+        found = true;
+        got = L.val;
+        break;
+      }
+    }
+    if (found)
+      for (uint32_t v = 0; v < (q.op_nv >> 8); ++v) in |= T.vals[q.vbeg + v] == got;
+    if (!sc_req_holds(q.op_nv & 0xFFu, found, in)) return false;
+  }
+  return true;
+}
+
 }  // namespace cg

@@ -151,6 +151,7 @@ class StagingPool {
 struct PolicyMapState;
 struct PrefilterState;
 struct IpcacheState;
+struct SelcacheState;
 struct HttpSnapshot;
 struct KafkaSnapshot;
 class HttpRing;
@@ -166,6 +167,7 @@ struct Engine {
   std::map<uint32_t, std::unique_ptr<PolicyMapState>> maps;
   std::map<uint32_t, std::unique_ptr<PrefilterState>> prefilters;
   std::map<uint32_t, std::unique_ptr<IpcacheState>> ipcaches;
+  std::map<uint32_t, std::unique_ptr<SelcacheState>> selcaches;
   std::shared_ptr<HttpSnapshot> http;
   std::shared_ptr<KafkaSnapshot> kafka;
   StagingPool staging;  // the "_host" entry points' buffers and streams

@@ -101,4 +101,12 @@ int launch_http_ring(const HttpDev& HT, const HttpRawDev& R, const HttpRingDev& 
 // the device's wall_clock64() into *d_out (ring.cc measures its rate)
 int ring_clock(unsigned long long* d_out, void* stream);
 
+// The selector cache (kernels_selcache.hip).  bits[T.n][I.words]: one ballot
+// word per (selector, 64-identity group), padding bits zero.
+int launch_selcache_match(const ScIdentDev& I, const ScSelDev& T, unsigned long long* bits, void* stream, int cus);
+// ing/eg[n][words], flags[n] for the endpoints eps[n] (identity indices; an
+// index >= n_ids yields zero rows).  R.M is the rule selectors' match matrix.
+int launch_selcache_reach(const ScRuleDev& R, uint32_t n_ids, uint32_t words, const uint32_t* eps, size_t n,
+                          unsigned long long* ing, unsigned long long* eg, uint8_t* flags, void* stream);
+
 }  // namespace cg

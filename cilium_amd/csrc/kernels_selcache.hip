@@ -1,0 +1,189 @@
+// kernels_selcache.hip — label selectors over the identity cache as bitsets
+// (selcache.h; EndpointSelector.Matches, pkg/policy/api/selector.go:279-310;
+// LabelArray.Get, pkg/labels/array.go:90-131; canReachIngress / canReachEgress,
+// pkg/policy/rule.go:352-440; GetRulesMatching, repository.go:624-643).
+//
+// selcache_match_kernel: one lane per identity, so a wave covers 64
+// consecutive identities and its __ballot is one output word.  Each lane
+// stages its first kScFast labels in registers once and then walks a chunk
+// of selectors: the requirement stream (selector headers, requirements,
+// value ids) is wave-uniform and read through scalar loads, the label scan
+// is per lane and branch-free (the staged labels are tested last to first, so
+// the first hit in the identity's order is the one that stays).  An identity
+// with more labels continues the scan in its global records.  Integer work
+// on registers; memory traffic is the label records once per block and chunk
+// and one 8-byte word per (selector, wave).
+//
+// selcache_reach_kernel: one block per (endpoint, 256 words).  The rules are
+// taken in tiles: the block first ballots, per 64 rules, whether the rule's
+// subject row has the endpoint's bit (the rule is "selected"), leaving one
+// mask word per 64 rules in LDS; then every thread walks the set bits — the
+// same in all lanes — and ORs the selected rules' allow rows and complemented
+// require rows at its word.  Both directions in one pass.  Bound by reading
+// rows of M, each read coalesced over the block's words.
+#include <hip/hip_runtime.h>
+
+#include "dev_types.h"
+#include "kernels.h"
+
+namespace cg {
+
+namespace {
+
+constexpr int kScFast = 8;             // labels staged in registers per identity
+constexpr int kMatchThreads = 1024;    // 16 waves: the block's words of one row fill a 128-byte line
+constexpr uint32_t kMatchChunk = 256;  // selectors per block at most
+constexpr int kReachThreads = 256;
+constexpr uint32_t kReachTile = 4096;  // rules per LDS tile (64 mask words)
+static_assert(kReachTile % kReachThreads == 0 && kReachThreads % 64 == 0, "whole waves ballot the tile");
+
+__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+
+__global__ __launch_bounds__(kMatchThreads) void selcache_match_kernel(ScIdentDev I, ScSelDev T, uint32_t chunk,
+                                                                       unsigned long long* __restrict__ bits) {
+  const uint32_t i = blockIdx.x * kMatchThreads + threadIdx.x;
+  const uint32_t w = uni(i >> 6);  // this wave's word: 64 consecutive identities
+  if (w >= I.words) return;        // whole waves past the table (nothing below synchronises the block)
+  const bool valid = i < I.n;
+  uint32_t lo = 0, nl = 0;
+  if (valid) {
+    lo = I.lab_off[i];
+    nl = I.lab_off[i + 1] - lo;
+  }
+  uint32_t lk[kScFast], ls[kScFast], lv[kScFast];
+#pragma unroll
+  for (int j = 0; j < kScFast; ++j) {
+    lk[j] = kScNoKey;  // an absent slot equals no selector key
+    ls[j] = 0;
+    lv[j] = 0;
+    if ((uint32_t)j < nl) {
+      const uint4 x = *reinterpret_cast<const uint4*>(I.labels + lo + j);
+      lk[j] = x.x;
+      ls[j] = x.y;
+      lv[j] = x.z;
+    }
+  }
+  const uint32_t s0 = blockIdx.y * chunk;
+  const uint32_t s1 = s0 + chunk < T.n ? s0 + chunk : T.n;
+  for (uint32_t s = s0; s < s1; ++s) {
+    const uint32_t su = uni(s);
+    const ScSel h = T.sels[su];
+    bool m = valid;
+    if (!(h.nreq & kScAlways)) {
+      const uint32_t nreq = uni(h.nreq), rbeg = uni(h.rbeg);
+      for (uint32_t r = 0; r < nreq; ++r) {
+        const uint4 qx = *reinterpret_cast<const uint4*>(T.reqs + uni(rbeg + r));
+        const uint32_t key = uni(qx.x), src = uni(qx.y), op_nv = uni(qx.z), vbeg = uni(qx.w);
+        bool found = false;
+        uint32_t got = 0;
+#pragma unroll
+        for (int j = kScFast - 1; j >= 0; --j) {  // last to first: the earliest hit is kept
+          const bool hit = sc_label_hit(lk[j], ls[j], key, src);
+          found = found || hit;
+          got = hit ? lv[j] : got;
+        }
+        if (nl > (uint32_t)kScFast && !found) {  // a long identity: its remaining records, in order
+          for (uint32_t j = kScFast; j < nl; ++j) {
+            const uint4 x = *reinterpret_cast<const uint4*>(I.labels + lo + j);
+            if (sc_label_hit(x.x, x.y, key, src)) {
+              found = true;
+              got = x.z;
+              break;
+            }
+          }
+        }
+        const uint32_t nv = op_nv >> 8;
+        bool in = false;
+        for (uint32_t v = 0; v < nv; ++v) in = in || T.vals[uni(vbeg + v)] == got;
+        in = in && found;
+        m = m && sc_req_holds(op_nv & 0xFFu, found, in);
+        if (__ballot(m) == 0ull) break;  // no identity of the wave can still match
+      }
+    }
+    const unsigned long long word = __ballot(m);  // lanes past the table vote 0: zero padding bits
+    if ((threadIdx.x & 63u) == 0) bits[(size_t)su * I.words + w] = word;
+  }
+}
+
+__global__ __launch_bounds__(kReachThreads) void selcache_reach_kernel(ScRuleDev R, uint32_t n_ids, uint32_t W,
+                                                                       const uint32_t* __restrict__ eps,
+                                                                       unsigned long long* __restrict__ ing,
+                                                                       unsigned long long* __restrict__ eg,
+                                                                       uint8_t* __restrict__ flags) {
+  __shared__ unsigned long long selmask[kReachTile / 64];
+  const uint32_t ei = blockIdx.y;
+  const uint32_t e = uni(eps[ei]);
+  const bool eok = e < n_ids;  // an index outside the table selects no rule
+  const uint32_t w = blockIdx.x * kReachThreads + threadIdx.x;
+  const bool live = w < W;
+  unsigned long long allow0 = 0, allow1 = 0, deny0 = 0, deny1 = 0;
+  uint32_t fl = 0;
+  for (uint32_t t0 = 0; t0 < R.n; t0 += kReachTile) {
+    // which rules of the tile select the endpoint: one mask word per 64 rules
+    for (uint32_t k = threadIdx.x; k < kReachTile; k += kReachThreads) {
+      const uint32_t r = t0 + k;
+      bool sel = false;
+      if (eok && r < R.n) sel = (R.M[(size_t)R.subject[r] * W + (e >> 6)] >> (e & 63u)) & 1ull;
+      const unsigned long long b = __ballot(sel);
+      if ((threadIdx.x & 63u) == 0) selmask[k >> 6] = b;
+    }
+    __syncthreads();
+    const uint32_t left = R.n - t0;
+    const uint32_t nw = ((left < kReachTile ? left : kReachTile) + 63u) >> 6;
+    for (uint32_t q = 0; q < nw; ++q) {
+      const unsigned long long mq = selmask[q];
+      unsigned long long mask = (unsigned long long)uni((uint32_t)mq) | ((unsigned long long)uni((uint32_t)(mq >> 32)) << 32);
+      while (mask) {
+        const uint32_t r = t0 + q * 64u + (uint32_t)__builtin_ctzll(mask);
+        mask &= mask - 1;
+        fl |= R.flags[r];
+        if (live) {
+          for (uint32_t x = R.req_off[0][r]; x < R.req_off[0][r + 1]; ++x) deny0 |= ~R.M[(size_t)R.req_idx[0][x] * W + w];
+          for (uint32_t x = R.allow_off[0][r]; x < R.allow_off[0][r + 1]; ++x) allow0 |= R.M[(size_t)R.allow_idx[0][x] * W + w];
+          for (uint32_t x = R.req_off[1][r]; x < R.req_off[1][r + 1]; ++x) deny1 |= ~R.M[(size_t)R.req_idx[1][x] * W + w];
+          for (uint32_t x = R.allow_off[1][r]; x < R.allow_off[1][r + 1]; ++x) allow1 |= R.M[(size_t)R.allow_idx[1][x] * W + w];
+        }
+      }
+    }
+    __syncthreads();  // the next tile overwrites the masks
+  }
+  if (live) {
+    const unsigned long long valid = (w == W - 1 && (n_ids & 63u)) ? (1ull << (n_ids & 63u)) - 1ull : ~0ull;
+    ing[(size_t)ei * W + w] = allow0 & ~deny0 & valid;
+    eg[(size_t)ei * W + w] = allow1 & ~deny1 & valid;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) flags[ei] = (uint8_t)fl;
+}
+
+}  // namespace
+
+int launch_selcache_match(const ScIdentDev& I, const ScSelDev& T, unsigned long long* bits, void* stream, int cus) {
+  if (I.n == 0 || T.n == 0) return 0;
+  const uint32_t gx = (I.n + kMatchThreads - 1) / kMatchThreads;
+  // selectors per block: as many as keeps every CU busy with a few blocks,
+  // and few enough blocks for the grid's y extent
+  uint32_t chunk = kMatchChunk;
+  const uint64_t want = 4ull * (uint64_t)(cus > 0 ? cus : 1);
+  while (chunk > 16 && (uint64_t)gx * ((T.n + chunk - 1) / chunk) < want) chunk >>= 1;
+  while ((T.n + chunk - 1) / chunk > 65535u) chunk <<= 1;
+  const dim3 g(gx, (T.n + chunk - 1) / chunk), b(kMatchThreads);
+  hipLaunchKernelGGL(selcache_match_kernel, g, b, 0, (hipStream_t)stream, I, T, chunk, bits);
+  return (int)hipGetLastError();
+}
+
+int launch_selcache_reach(const ScRuleDev& R, uint32_t n_ids, uint32_t words, const uint32_t* eps, size_t n,
+                          unsigned long long* ing, unsigned long long* eg, uint8_t* flags, void* stream) {
+  if (n == 0) return 0;
+  const uint32_t gx = words ? (words + kReachThreads - 1) / kReachThreads : 1;  // no identities: flags only
+  for (size_t off = 0; off < n; off += 65535) {
+    const size_t cnt = n - off < 65535 ? n - off : 65535;
+    const dim3 g(gx, (unsigned)cnt), b(kReachThreads);
+    hipLaunchKernelGGL(selcache_reach_kernel, g, b, 0, (hipStream_t)stream, R, n_ids, words, eps + off,
+                       ing + off * words, eg + off * words, flags + off);
+    const int err = (int)hipGetLastError();
+    if (err) return err;
+  }
+  return 0;
+}
+
+}  // namespace cg

@@ -1,0 +1,96 @@
+// selcache.h — the selector cache: the identity cache and a rule set's
+// selectors compiled to interned-id tables (dev_types.h Sc*), so that
+// "which identities does this selector select" (getSecurityIdentities,
+// pkg/endpoint/policy.go:93-106) and "which identities may this endpoint
+// reach at L3" (computeDesiredL3PolicyMapEntries, :298-371) are bitset
+// kernels (kernels_selcache.hip) instead of per-identity label walks.
+#pragma once
+
+#include <memory>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "dev_types.h"
+#include "engine.h"
+
+namespace cg {
+
+// The identity cache, compiled: CSR label records in the given order and the
+// string → id dictionary that selectors are interned against.
+struct ScIdentSnap {
+  std::vector<uint32_t> ids;
+  std::vector<uint32_t> lab_off{0};
+  std::vector<ScLabel> labels;
+  std::unordered_map<std::string, uint32_t> dict;  // ids from 1; "any" is kScAny and not stored
+  uint32_t n = 0, words = 0;
+  ScIdentDev view() const { return {lab_off.data(), labels.data(), n, words}; }
+};
+
+// Selectors as given (strings), kept so they can be interned again when the
+// identity cache — and with it the dictionary — is replaced.
+struct ScSelSrc {
+  struct Req {
+    std::string key, src;  // "source:key" split; src "any" when there is no colon
+    uint8_t op;
+    std::vector<std::string> vals;
+  };
+  std::vector<Req> reqs;
+  bool always = false;  // the empty selector, or matchLabels holds reserved:all
+};
+
+struct ScSelTab {
+  std::vector<ScSel> sels;
+  std::vector<ScReq> reqs;
+  std::vector<uint32_t> vals;
+  ScSelDev view() const { return {sels.data(), reqs.data(), vals.data(), (uint32_t)sels.size()}; }
+};
+
+struct ScRuleSrc {
+  std::vector<ScSelSrc> sels;
+  std::vector<uint32_t> subject;
+  std::vector<uint8_t> flags;
+  std::vector<uint32_t> req_off[2], req_idx[2], allow_off[2], allow_idx[2];
+  uint32_t n = 0;
+};
+
+// Validating compilers of the C ABI's arguments (fail with CG_INVALID_ARGUMENT
+// on malformed offsets or indices, CG_POLICY_REJECTED on an unknown operator).
+std::shared_ptr<const ScIdentSnap> sc_compile_identities(const uint32_t* ids, size_t n, const uint32_t* label_off,
+                                                         const uint8_t* key_blob, const uint64_t* key_off,
+                                                         const uint8_t* val_blob, const uint64_t* val_off);
+std::vector<ScSelSrc> sc_parse_selectors(const cg_selector_table& t);
+std::shared_ptr<const ScRuleSrc> sc_parse_rules(const cg_selector_table& sels, const cg_selcache_rules& rules);
+// Interns against the identities' dictionary; a string no identity carries
+// gets an id past the dictionary's.
+ScSelTab sc_compile_selectors(const ScIdentSnap& idents, const std::vector<ScSelSrc>& sels);
+
+// Host walkers over the compiled tables (cg_diag_selcache_*): what the
+// kernels compute, on `threads` CPU threads.
+void sc_match_host(const ScIdentDev& I, const ScSelDev& T, uint64_t* bits, uint32_t threads);
+void sc_reach_host(const ScRuleDev& R, uint32_t n_ids, uint32_t words, const uint32_t* eps, size_t n, uint64_t* ing,
+                   uint64_t* eg, uint8_t* flags, uint32_t threads);
+
+// One published build: the host tables and, on a GPU handle, their device
+// copies with the rule selectors' match matrix M already computed.
+struct ScPublished {
+  std::shared_ptr<const ScIdentSnap> idents;
+  std::shared_ptr<const ScRuleSrc> rules;
+  ScSelTab seltab;                // rules->sels interned against idents
+  std::vector<uint64_t> host_m;   // M on the host, filled by the first diag reach
+  std::shared_ptr<DevTables> tab; // device copies (engine.h)
+  ScIdentDev dI{};
+  ScSelDev dT{};
+  ScRuleDev dR{};
+  ScRuleDev host_rules() const;   // over host_m
+};
+
+struct SelcacheState {
+  std::shared_ptr<const ScIdentSnap> idents = std::make_shared<ScIdentSnap>();
+  std::shared_ptr<const ScRuleSrc> rules = std::make_shared<ScRuleSrc>();
+  bool dirty = true;
+  std::shared_ptr<ScPublished> pub;
+  void rebuild(Engine& e);
+};
+
+}  // namespace cg

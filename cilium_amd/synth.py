@@ -624,3 +624,96 @@ def http10k_requests_fast(n: int, info: dict, seed: int = SEED, raw: bool = Fals
             "port": np.concatenate(ports) if ports else np.zeros(0, np.uint16),
             "remote": np.concatenate(remotes).astype(np.uint32) if remotes else np.zeros(0, np.uint32),
             key[0]: blob, key[1]: off}
+
+
+# ------------------------------------------ selector cache (cilium_amd.selcache)
+# k8s-style labels: (source:key, vocabulary size, value prefix); values are
+# Zipf-distributed over the vocabulary, so a few apps / namespaces are large.
+LABEL_KEYS = [("k8s:app", 2000, "app"), ("k8s:tier", 4, "tier"), ("k8s:env", 3, "env"),
+              ("k8s:io.kubernetes.pod.namespace", 200, "ns"), ("k8s:io.cilium.k8s.policy.cluster", 3, "cluster"),
+              ("k8s:team", 50, "team"), ("container:version", 20, "v"), ("any:zone", 6, "zone")]
+
+
+def _zipf(rng, n: int, vocab: int, a: float = 1.3) -> np.ndarray:
+    return ((rng.zipf(a, n) - 1) % vocab).astype(np.int64)  # the tail wraps, value 0 stays the largest
+
+
+def _label_value(prefix: str, v: int) -> str:
+    if prefix == "cluster":  # the local cluster's name is the common one (resolve.DEFAULT_CLUSTER_NAME)
+        return "default" if v == 0 else f"cluster{v}"
+    return f"{prefix}{v}"
+
+
+def identity_cache(n: int = 65536, seed: int = SEED, n_labels: int = 8, first_id: int = 256) -> dict:
+    """{identity: {"source:key": value}}: n identities numbered from first_id
+    with the first n_labels of LABEL_KEYS each, in that order."""
+    rng = np.random.default_rng(seed)
+    keys = LABEL_KEYS[:n_labels]
+    cols = [_zipf(rng, n, vocab) for _, vocab, _ in keys]
+    names = [[_label_value(p, v) for v in range(vocab)] for _, vocab, p in keys]
+    return {first_id + i: {k[0]: names[j][cols[j][i]] for j, k in enumerate(keys)} for i in range(n)}
+
+
+def label_repository(n_rules: int = 10000, seed: int = SEED):
+    """A resolve.Repository of n_rules label-based rules over LABEL_KEYS: each
+    selects an app (sometimes narrowed by env or namespace, sometimes by an
+    expression), allows peers by app / namespace / tier+env / expressions on
+    ingress and (half of them) egress; a third of the direction rules carry
+    ToPorts (so they allow nothing at L3), a few carry FromRequires /
+    ToRequires or entities."""
+    from . import resolve as R
+    rng = np.random.default_rng(seed ^ 0x5E1C)
+
+    def val(j: int) -> str:
+        _, vocab, p = LABEL_KEYS[j]
+        return _label_value(p, int(_zipf(rng, 1, vocab)[0]))
+
+    def key(j: int) -> str:
+        k = LABEL_KEYS[j][0]
+        return k if rng.random() < 0.8 else "any:" + k.split(":", 1)[1]
+
+    def peer() -> "R.EndpointSelector":
+        t = rng.random()
+        if t < 0.45:
+            return R.EndpointSelector.of({key(0): val(0)})
+        if t < 0.65:
+            return R.EndpointSelector.of({key(3): val(3)})
+        if t < 0.8:
+            return R.EndpointSelector.of({key(1): val(1), key(2): val(2)})
+        if t < 0.9:
+            return R.EndpointSelector.of({key(3): val(3)}, [(key(1), "NotIn", (val(1),))])
+        if t < 0.97:
+            return R.EndpointSelector.of(None, [(key(5), "In", (val(5), val(5), val(5))), (key(7), "Exists", ())])
+        return R.EndpointSelector.of(None, [(key(6), "DoesNotExist", ())])
+
+    def require() -> "R.EndpointSelector":
+        if rng.random() < 0.5:
+            return R.EndpointSelector.of(None, [(key(2), "In", ("env0", "env1"))])
+        return R.EndpointSelector.of({key(4): "default"})
+
+    def ports():
+        return [R.PortRule([R.PortProtocol(str(int(rng.choice([80, 443, 8080, 9092]))), "TCP")])]
+
+    def direction(cls):
+        out = []
+        for _ in range(int(rng.integers(1, 3))):
+            peers = [peer() for _ in range(int(rng.integers(1, 4)))]
+            req = [require()] if rng.random() < 0.05 else []
+            ent = [str(rng.choice(["world", "cluster", "host"]))] if rng.random() < 0.05 else []
+            tp = ports() if rng.random() < 0.33 else []
+            out.append(cls(peers, req, ent, tp))
+        return out
+
+    rules = []
+    for _ in range(n_rules):
+        t = rng.random()
+        if t < 0.6:
+            subj = R.EndpointSelector.of({key(0): val(0)})
+        elif t < 0.8:
+            subj = R.EndpointSelector.of({key(0): val(0), key(2): val(2)})
+        elif t < 0.95:
+            subj = R.EndpointSelector.of({key(3): val(3)})
+        else:
+            subj = R.EndpointSelector.of({key(3): val(3)}, [(key(1), "In", (val(1), val(1)))])
+        rules.append(R.Rule(subj, direction(R.IngressRule), direction(R.EgressRule) if rng.random() < 0.5 else []))
+    return R.Repository(rules)

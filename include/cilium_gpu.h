@@ -726,6 +726,94 @@ enum { CG_REGEX_ECMA = 0, CG_REGEX_GO = 1 };
 int cg_regex_validate(const char* re, size_t re_len, uint32_t flavour);
 
 /* ======================================================================== */
+/* Selector cache: label selectors -> identity sets, and L3 reachability    */
+/* (getSecurityIdentities, pkg/endpoint/policy.go:93-106;                   */
+/* computeDesiredL3PolicyMapEntries, :298-371; EndpointSelector.Matches,    */
+/* pkg/policy/api/selector.go:279-310; LabelArray.Get,                      */
+/* pkg/labels/array.go:90-131; canReachIngress / canReachEgress,            */
+/* pkg/policy/rule.go:352-440; GetRulesMatching, repository.go:624-643)     */
+/* ======================================================================== */
+
+/* Requirement operators.  MATCH_LABEL is a matchLabels pair (one value, may
+ * be ""); the others are the matchExpressions operators.  Any other value is
+ * refused with CG_POLICY_REJECTED. */
+enum {
+  CG_SEL_MATCH_LABEL = 0,
+  CG_SEL_IN = 1,
+  CG_SEL_NOT_IN = 2,
+  CG_SEL_EXISTS = 3,
+  CG_SEL_DOES_NOT_EXIST = 4
+};
+
+/* A table of selectors.  Selector s owns the requirements
+ * [req_off[s], req_off[s+1]); requirement r has the key string
+ * key_blob[key_off[r] .. key_off[r+1]) ("source:key"; without a colon the
+ * source is "any"), the operator ops[r], and the value strings
+ * [val_off[r], val_off[r+1]), value v being val_blob[val_str_off[v] ..
+ * val_str_off[v+1]).  A selector without requirements, or with a MATCH_LABEL
+ * key exactly "reserved:all", selects every identity. */
+typedef struct {
+  size_t n_selectors;
+  const uint32_t* req_off;      /* n_selectors + 1 */
+  const uint8_t* ops;           /* per requirement: CG_SEL_* */
+  const uint8_t* key_blob;
+  const uint64_t* key_off;      /* requirements + 1 */
+  const uint32_t* val_off;      /* requirements + 1 */
+  const uint8_t* val_blob;
+  const uint64_t* val_str_off;  /* values + 1 */
+} cg_selector_table;
+
+/* A rule set over a selector table, per direction d (0 ingress, 1 egress):
+ * rule r's "require" selectors are req_idx[d][req_off[d][r] .. req_off[d][r+1])
+ * (FromRequires / ToRequires of all its direction rules) and its "allow"
+ * selectors allow_idx[d][...] (the source / destination selectors, entities
+ * included, of its direction rules without ToPorts). */
+typedef struct {
+  size_t n_rules;
+  const uint32_t* subject;       /* n_rules: the rule's EndpointSelector */
+  const uint8_t* dir_flags;      /* n_rules: bit 0 has ingress rules, bit 1 has egress rules */
+  const uint32_t* req_off[2];    /* n_rules + 1 each */
+  const uint32_t* req_idx[2];
+  const uint32_t* allow_off[2];  /* n_rules + 1 each */
+  const uint32_t* allow_idx[2];
+} cg_selcache_rules;
+
+int cg_selcache_create(uint64_t h, uint32_t* sc_id);
+int cg_selcache_destroy(uint64_t h, uint32_t sc_id);
+/* The identity cache, replaced as a whole: identity i (ids[i]) has the labels
+ * [label_off[i], label_off[i+1]) in the given order, label l being the key
+ * key_blob[key_off[l] .. key_off[l+1]) ("source:key") and the value
+ * val_blob[val_off[l] .. val_off[l+1]).  Bit positions of every result
+ * follow this order. */
+int cg_selcache_set_identities(uint64_t h, uint32_t sc_id, const uint32_t* ids, size_t n,
+                               const uint32_t* label_off, const uint8_t* key_blob, const uint64_t* key_off,
+                               const uint8_t* val_blob, const uint64_t* val_off);
+/* The rule set and its selectors, replaced as a whole (all or nothing). */
+int cg_selcache_set_rules(uint64_t h, uint32_t sc_id, const cg_selector_table* sels,
+                          const cg_selcache_rules* rules);
+/* sizes of the current tables: identities, words per row (ceil(n / 64)),
+ * selectors of the rule set, rules */
+int cg_selcache_info(uint64_t h, uint32_t sc_id, size_t* n_identities, size_t* words, size_t* n_selectors,
+                     size_t* n_rules);
+/* bits[S][W]: bit i of word w of row s says whether selector s selects
+ * identity 64*w + i; the padding bits of the last word are zero.  sels (a
+ * HOST table in both variants) may be NULL: the rule set's selectors.
+ * cap_words: room in bits (>= S * W). */
+int cg_selcache_match_dev(uint64_t h, uint32_t sc_id, const cg_selector_table* sels, uint64_t* d_bits,
+                          size_t cap_words, void* stream);
+int cg_selcache_match_host(uint64_t h, uint32_t sc_id, const cg_selector_table* sels, uint64_t* bits,
+                           size_t cap_words);
+/* Per endpoint e (an index into the identity table): the identities it
+ * accepts at L3 on ingress ing[e][W] and may reach on egress eg[e][W]
+ * (AllowsIngressLabelAccess / AllowsEgressLabelAccess against every
+ * identity), and flags[e] (bit 0 ingress, bit 1 egress enforcement:
+ * GetRulesMatching). */
+int cg_selcache_reach_dev(uint64_t h, uint32_t sc_id, const uint32_t* d_endpoints, size_t n, uint64_t* d_ing,
+                          uint64_t* d_eg, uint8_t* d_flags, void* stream);
+int cg_selcache_reach_host(uint64_t h, uint32_t sc_id, const uint32_t* endpoints, size_t n, uint64_t* ing,
+                           uint64_t* eg, uint8_t* flags);
+
+/* ======================================================================== */
 /* Diagnostics (CPU test-suite only; no verdict entry point calls these)    */
 /* ======================================================================== */
 /* Compile `re` with the engine's regex compiler and run the DFA on s
@@ -755,6 +843,13 @@ int cg_diag_ipcache_eval_host(uint64_t h, uint32_t ipc_id, const uint32_t* v4, s
                               cg_remote_endpoint_info* out6);
 int cg_diag_prefilter_eval_host(uint64_t h, uint32_t pf_id, const uint32_t* v4, size_t n4,
                                 uint8_t* out4, const uint8_t* v6, size_t n6, uint8_t* out6);
+/* The selector cache's compiled tables walked on the host (threads: worker
+ * threads, 0 = 1); same arguments and results as cg_selcache_match_host /
+ * cg_selcache_reach_host.  They also work on a handle without a GPU. */
+int cg_diag_selcache_match_host(uint64_t h, uint32_t sc_id, const cg_selector_table* sels, uint64_t* bits,
+                                size_t cap_words, uint32_t threads);
+int cg_diag_selcache_reach_host(uint64_t h, uint32_t sc_id, const uint32_t* endpoints, size_t n, uint64_t* ing,
+                                uint64_t* eg, uint8_t* flags, uint32_t threads);
 
 #ifdef __cplusplus
 }

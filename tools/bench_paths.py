@@ -8,6 +8,8 @@ configs, one JSON line each (bench.py covers config 5, the 10K-rule HTTP set):
 * L4 with ipcache identities: config 2's map, identities resolved in-kernel
 * proxylib r2d2: 512 r2d2 rules over 64 ports, ~100M requests
   on the HTTP kernel
+* selcache (opt-in, --paths selcache): selector x identity matching and L3
+  reach, 65,536 identities, a 10,000-rule repository, 256 endpoints
 
 Inputs are resident in HBM before timing; kernels are timed with HIP events
 on their stream.  Each line carries the kernel's HBM roofline (algorithmic
@@ -731,6 +733,91 @@ def bench_cassandra(torch, dev, stream, cl, args, threads):
                                   400)
 
 
+def bench_selcache(torch, dev, stream, cl, args, threads):
+    """The selector cache at regeneration scale: 65,536 identities of 8
+    labels, a 10,000-rule label repository, 256 endpoints.  Both kernels are
+    checked against the library's host walker of the same compiled tables
+    (cg_diag_selcache_*_host on `threads` threads — that run is also the CPU
+    leg), then timed on the stream.  resolve.py (the Python restatement the
+    tables are pinned to) is timed on a sample of cells and extrapolated."""
+    from cilium_amd import synth
+    N_IDS, N_RULES, E = 65536, 10000, 256
+    cache = synth.identity_cache(N_IDS)
+    repo = synth.label_repository(N_RULES)
+    sc = cl.selector_cache()
+    sc.set_identities(cache)
+    sc.set_repository(repo)
+    info = sc.info()
+    S, W = info["selectors"], info["words"]
+    rng = np.random.default_rng(0x5E1)
+    eps = np.sort(rng.choice(N_IDS, E, replace=False)).astype(np.uint32)
+    # ---- check, and the host walker's time on the same tables
+    got_m = sc.match(None)
+    t0 = time.perf_counter()
+    want_m = sc.match(None, diag_cpu=True, threads=threads)
+    cpu_match_s = time.perf_counter() - t0
+    assert np.array_equal(got_m, want_m), "selcache match differs from the host walker"
+    got_r = sc.reach_indices(eps)
+    sc.reach_indices(eps[:1], diag_cpu=True, threads=threads)  # builds the walker's own M (not timed below)
+    t0 = time.perf_counter()
+    want_r = sc.reach_indices(eps, diag_cpu=True, threads=threads)
+    cpu_reach_s = time.perf_counter() - t0
+    assert all(np.array_equal(a, b) for a, b in zip(got_r, want_r)), "selcache reach differs from the host walker"
+    # ---- kernels
+    d_m = torch.empty(S * W, dtype=torch.int64, device=dev)
+    d_ep = torch.from_numpy(eps.view(np.int32)).to(dev)
+    d_ing = torch.empty(E * W, dtype=torch.int64, device=dev)
+    d_eg = torch.empty(E * W, dtype=torch.int64, device=dev)
+    d_fl = torch.empty(E, dtype=torch.uint8, device=dev)
+    match_s = timed(torch, stream, lambda: sc.match_dev(None, d_m, stream=stream.cuda_stream), args.steps, 2)
+    reach_s = timed(torch, stream, lambda: sc.reach_dev(d_ep, E, d_ing, d_eg, d_fl, stream=stream.cuda_stream),
+                    args.steps, 2)
+    assert np.array_equal(d_m.cpu().numpy().view(np.uint64).reshape(S, W), want_m)
+    # ---- resolve.py on a sample, extrapolated
+    py_match = py_reach = None
+    if args.cpu_seconds > 0:
+        sels = sc.compile_repository(repo)[0]
+        labels = list(cache.values())
+        ss, ii = rng.integers(0, S, 100_000), rng.integers(0, N_IDS, 100_000)
+        t0 = time.perf_counter()
+        for a, b in zip(ss, ii):
+            sels[a].matches(labels[b])
+        py_match = len(ss) / (time.perf_counter() - t0)
+        t0, k = time.perf_counter(), 0
+        while time.perf_counter() - t0 < min(args.cpu_seconds, 5.0):
+            me, peer = labels[int(eps[k % E])], labels[int(rng.integers(0, N_IDS))]
+            repo.allows_ingress_label_access(peer, me)
+            repo.allows_egress_label_access(me, peer)
+            k += 1
+        py_reach = 2 * k / (time.perf_counter() - t0)
+    cells, rcells = S * N_IDS, 2 * E * N_IDS
+    ident_bytes = N_IDS * 8 * 16 + (N_IDS + 1) * 4
+    out = line("selector x identity cells/s (selcache_match_kernel: EndpointSelector.Matches over the identity cache)",
+               cells, match_s, (S * W * 8 + ident_bytes) / cells, "selcache_match_kernel", cells / cpu_match_s,
+               f"the same tables walked by cg_diag_selcache_match_host on {threads} threads, one full pass", threads,
+               {"unit": "cells/s",
+                "config": {"workload": "65,536 identities x 8 labels, 10,000-rule label repository, 256 endpoints",
+                           "identities": N_IDS, "rules": N_RULES, "selectors": S, "endpoints": E},
+                "match": {"kernel_ms": match_s * 1e3, "gcells_per_s": cells / match_s / 1e9,
+                          "output_bytes": S * W * 8, "output_gbps": S * W * 8 / match_s / 1e9,
+                          "output_frac_of_hbm_peak": S * W * 8 / match_s / 1e9 / HBM_PEAK_GBPS,
+                          "host_walker_ms": cpu_match_s * 1e3, "host_walker_threads": threads,
+                          "gpu_over_host_walker": cpu_match_s / match_s},
+                "reach": {"kernel": "selcache_reach_kernel", "kernel_ms": reach_s * 1e3,
+                          "gcells_per_s": rcells / reach_s / 1e9, "output_bytes": 2 * E * W * 8 + E,
+                          "output_gbps": (2 * E * W * 8 + E) / reach_s / 1e9,
+                          "output_frac_of_hbm_peak": (2 * E * W * 8 + E) / reach_s / 1e9 / HBM_PEAK_GBPS,
+                          "host_walker_ms": cpu_reach_s * 1e3, "host_walker_threads": threads,
+                          "gpu_over_host_walker": cpu_reach_s / reach_s},
+                "python_resolve": {"kind": "extrapolated from a sample (single thread)",
+                                   "match_cells_per_s": py_match, "match_sample_cells": 100_000,
+                                   "match_full_s_extrapolated": cells / py_match if py_match else None,
+                                   "reach_cells_per_s": py_reach,
+                                   "reach_full_s_extrapolated": rcells / py_reach if py_reach else None}})
+    sc.destroy()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--paths", default="l4,lpm,kafka,ipcache,proxylib,l4ipc")
@@ -749,7 +836,7 @@ def main():
     fns = {"l4": bench_l4, "lpm": bench_lpm, "kafka": bench_kafka, "ipcache": bench_ipcache,
            "proxylib": bench_proxylib, "l4ipc": bench_l4ipc, "kafkawire": bench_kafka_wire, "httphost": bench_http_host, "httpraw": bench_http_raw,
            "httpfields": bench_http_fields, "memcache": bench_memcache, "cassandra": bench_cassandra,
-           "kafkawirez": lambda *a: bench_kafka_wire(*a, codec_frac=0.5)}
+           "kafkawirez": lambda *a: bench_kafka_wire(*a, codec_frac=0.5), "selcache": bench_selcache}
     for p in args.paths.split(","):
         print(json.dumps(fns[p](torch, dev, stream, cl, args, threads)), flush=True)
     cl.close()
