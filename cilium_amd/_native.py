@@ -59,6 +59,7 @@ CG_KAFKA_DECODE_OK, CG_KAFKA_DECODE_ERROR = 0, 1
 CG_KAFKA_V_DENY, CG_KAFKA_V_ALLOW, CG_KAFKA_V_CLOSE = 0, 1, 2
 
 CG_SEL_MATCH_LABEL, CG_SEL_IN, CG_SEL_NOT_IN, CG_SEL_EXISTS, CG_SEL_DOES_NOT_EXIST = 0, 1, 2, 3, 4
+CG_EXP_ALL = 0x1
 
 
 class CiliumGPUError(RuntimeError):
@@ -98,6 +99,11 @@ class SelcacheRulesC(C.Structure):
     _fields_ = [("n_rules", C.c_size_t), ("subject", C.c_void_p), ("dir_flags", C.c_void_p),
                 ("req_off", C.c_void_p * 2), ("req_idx", C.c_void_p * 2),
                 ("allow_off", C.c_void_p * 2), ("allow_idx", C.c_void_p * 2)]
+
+
+class ExpandTableC(C.Structure):
+    """cg_expand_table"""
+    _fields_ = [("n_rows", C.c_size_t), ("rows", C.c_void_p), ("src_off", C.c_void_p), ("src_idx", C.c_void_p)]
 
 
 # Exported symbols and their signatures: (restype, argtypes)
@@ -203,6 +209,15 @@ SIGNATURES = {
     "cg_selcache_reach_host": (C.c_int, [_u64, _u32, _p, _sz, _p, _p, _p]),
     "cg_diag_selcache_match_host": (C.c_int, [_u64, _u32, C.POINTER(SelectorTableC), _p, _sz, _u32]),
     "cg_diag_selcache_reach_host": (C.c_int, [_u64, _u32, _p, _sz, _p, _p, _p, _u32]),
+    "cg_selcache_expand_dev": (C.c_int, [_u64, _u32, C.POINTER(ExpandTableC), _p, _sz, _p, _p, _p, _sz, _p, _p]),
+    "cg_selcache_expand_host": (C.c_int, [_u64, _u32, C.POINTER(ExpandTableC), _p, _sz, _p, _p, _p, _sz, _p]),
+    "cg_selcache_entries_host": (C.c_int, [_u64, _u32, C.POINTER(SelectorTableC), _p, _sz, C.POINTER(ExpandTableC),
+                                           _p, _p, _p, _sz, _p, _p]),
+    "cg_diag_selcache_expand_host": (C.c_int, [_u64, _u32, C.POINTER(ExpandTableC), _p, _sz, _p, _p, _p, _sz, _p,
+                                               _u32]),
+    "cg_diag_selcache_entries_host": (C.c_int, [_u64, _u32, C.POINTER(SelectorTableC), _p, _sz,
+                                                C.POINTER(ExpandTableC), _p, _p, _p, _sz, _p, _p, _u32]),
+    "cg_policymap_sync": (C.c_int, [_u64, _u32, _p, _p, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
 }
 
 

@@ -531,6 +531,22 @@ class PolicyMap:
         ports_be = np.ascontiguousarray(ports_be, np.uint16)
         N.check(N.lib.cg_policymap_allow(self.cl.h, self.id, _p(keys), _p(ports_be), len(keys)))
 
+    def sync(self, keys: np.ndarray, ports_be: np.ndarray) -> tuple[int, int]:
+        """syncPolicyMap (pkg/endpoint/endpoint.go:2621-2701) as one call: the
+        map holds exactly these raw entries (network byte order) afterwards.
+        Returns (added or rewritten, deleted); surviving keys keep their
+        counters, a key given twice takes its last value, and too many
+        distinct keys (CG_MAP_FULL) leave the map as it was."""
+        keys = np.ascontiguousarray(keys, POLICY_KEY_DTYPE)
+        ports_be = np.ascontiguousarray(ports_be, np.uint16)
+        if len(keys) != len(ports_be):
+            raise ValueError("keys and ports_be differ in length")
+        added, deleted = C.c_size_t(), C.c_size_t()
+        N.check(N.lib.cg_policymap_sync(self.cl.h, self.id, _p(keys) if len(keys) else None,
+                                        _p(ports_be) if len(keys) else None, len(keys),
+                                        C.byref(added), C.byref(deleted)))
+        return added.value, deleted.value
+
     def exists(self, identity: int, dport: int, proto: int, direction: int) -> bool:
         return self.lookup(PolicyKey(identity, htons(dport), proto, int(direction))) is not None
 

@@ -346,6 +346,79 @@ int cg_policymap_flush(uint64_t h, uint32_t map_id) {
   });
 }
 
+int cg_policymap_sync(uint64_t h, uint32_t map_id, const cg_policy_key* keys, const uint16_t* ports_be, size_t n,
+                      size_t* added, size_t* deleted) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    PolicyMapState& m = get_map(*e, map_id);
+    if (n && (!keys || !ports_be)) fail(CG_INVALID_ARGUMENT, "NULL keys/ports");
+    // the wanted state: distinct keys in first-appearance order, last value
+    std::unordered_map<uint64_t, uint16_t> want;
+    std::vector<uint64_t> seq;
+    want.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+      const uint64_t k = l4_key(keys[i]);
+      if (k == kL4EmptyKey) fail(CG_INVALID_ARGUMENT, "reserved all-ones policy key");
+      auto [it, fresh] = want.emplace(k, ports_be[i]);
+      if (fresh)
+        seq.push_back(k);
+      else
+        it->second = ports_be[i];
+    }
+    if (want.size() > m.max_entries) fail(CG_MAP_FULL, "policy map full (E2BIG)");
+    // nothing below fails: deletes first, so that their counter slots are free
+    size_t n_del = 0, n_add = 0;
+    std::vector<uint64_t> order;
+    order.reserve(want.size());
+    for (uint64_t k : m.order) {
+      if (want.count(k)) {
+        order.push_back(k);
+        continue;
+      }
+      auto it = m.entries.find(k);
+      m.free_ids.push_back(it->second.id);
+      m.entries.erase(it);
+      ++n_del;
+    }
+    std::vector<uint32_t> fresh_ids;
+    for (uint64_t k : seq) {
+      const uint16_t port = want[k];
+      auto it = m.entries.find(k);
+      if (it != m.entries.end()) {
+        if (it->second.proxy_port_be != port) {
+          it->second.proxy_port_be = port;
+          ++n_add;
+        }
+        continue;
+      }
+      uint32_t id;
+      if (!m.free_ids.empty()) {
+        id = m.free_ids.back();
+        m.free_ids.pop_back();
+      } else {
+        id = m.next_id++;
+      }
+      fresh_ids.push_back(id);
+      m.entries[k] = {port, id};
+      order.push_back(k);
+      ++n_add;
+    }
+    m.order = std::move(order);
+    if (n_add || n_del) m.dirty = true;
+    if (added) *added = n_add;
+    if (deleted) *deleted = n_del;
+    // new keys count from zero: clear their slots, one memset per run of ids
+    std::sort(fresh_ids.begin(), fresh_ids.end());
+    for (size_t i = 0; i < fresh_ids.size();) {
+      size_t j = i + 1;
+      while (j < fresh_ids.size() && fresh_ids[j] == fresh_ids[j - 1] + 1) ++j;
+      m.zero_counters(*e, fresh_ids[i], (uint32_t)(j - i));
+      i = j;
+    }
+  });
+}
+
 // A map's published tables, copied under the handle lock and held while the
 // launch is enqueued (engine.h DevTables).
 struct L4View {
@@ -1001,23 +1074,207 @@ int cg_diag_selcache_match_host(uint64_t h, uint32_t sc_id, const cg_selector_ta
   });
 }
 
+// The rule selectors' matrix on the host, once per snapshot.
+static void sc_ensure_host_m(Engine& e, ScPublished& p, uint32_t threads) {
+  std::lock_guard<std::mutex> lk(e.mu);
+  const size_t need = p.seltab.sels.size() * (size_t)p.idents->words;
+  if (p.host_m.size() != need || !need) {
+    p.host_m.assign(std::max<size_t>(need, 1), 0);
+    sc_match_host(p.idents->view(), p.seltab.view(), p.host_m.data(), threads);
+    if (!need) p.host_m.resize(1);
+  }
+}
+
 int cg_diag_selcache_reach_host(uint64_t h, uint32_t sc_id, const uint32_t* endpoints, size_t n, uint64_t* ing,
                                 uint64_t* eg, uint8_t* flags, uint32_t threads) {
   return guarded([&] {
     auto e = get(h);
     const auto p = sc_pub(*e, sc_id);
     sc_check_endpoints(*p, endpoints, n, ing, eg, flags);
-    {
-      // the rule selectors' matrix on the host, once per snapshot
-      std::lock_guard<std::mutex> lk(e->mu);
-      const size_t need = p->seltab.sels.size() * (size_t)p->idents->words;
-      if (p->host_m.size() != need || !need) {
-        p->host_m.assign(std::max<size_t>(need, 1), 0);
-        sc_match_host(p->idents->view(), p->seltab.view(), p->host_m.data(), threads);
-        if (!need) p->host_m.resize(1);
-      }
-    }
+    sc_ensure_host_m(*e, *p, threads);
     sc_reach_host(p->host_rules(), p->idents->n, p->idents->words, endpoints, n, ing, eg, flags, threads);
+  });
+}
+
+// ---- expansion into policy-map entries
+static void sc_check_expand_out(const cg_expand_table* table, const void* row_off, const void* keys,
+                                const void* proxy, size_t cap) {
+  if (!table) fail(CG_INVALID_ARGUMENT, "selcache expand: NULL table");
+  if (!row_off) fail(CG_INVALID_ARGUMENT, "selcache expand: NULL row_off");
+  if (cap && (!keys || !proxy)) fail(CG_INVALID_ARGUMENT, "selcache expand: NULL keys/proxy");
+  if (cap > (1ull << 40)) fail(CG_INVALID_ARGUMENT, "selcache expand: cap_entries out of range");
+}
+
+static ScExpDev sc_exp_view(const ScPublished& p, const ScExpRow* rows, const uint32_t* src_idx, size_t n_rows,
+                            const uint32_t* ids, const uint64_t* src) {
+  ScExpDev X{};
+  X.rows = rows;
+  X.src_idx = src_idx;
+  X.ids = ids;
+  X.src = reinterpret_cast<const unsigned long long*>(src);
+  X.n_rows = (uint32_t)n_rows;
+  X.n_ids = p.idents->n;
+  X.words = p.idents->words;
+  return X;
+}
+
+int cg_selcache_expand_dev(uint64_t h, uint32_t sc_id, const cg_expand_table* table, const uint64_t* d_src,
+                           size_t src_rows, uint64_t* d_row_off, cg_policy_key* d_keys, uint16_t* d_proxy,
+                           size_t cap_entries, uint64_t* d_total, void* stream) {
+  return guarded([&] {
+    auto e = get(h);
+    e->require_gpu();
+    sc_check_expand_out(table, d_row_off, d_keys, d_proxy, cap_entries);
+    if ((uintptr_t)d_keys & 7u) fail(CG_INVALID_ARGUMENT, "selcache expand: d_keys is not 8-byte aligned");
+    const auto p = sc_pub(*e, sc_id);
+    const ScExpTab t = sc_compile_expand(*table, src_rows);
+    if (!t.src_idx.empty() && p->idents->words && !d_src) fail(CG_INVALID_ARGUMENT, "selcache expand: NULL source matrix");
+    e->set_device();
+    void* st = stream_of(*e, stream);
+    auto tmp = std::make_shared<DevTables>();
+    const ScExpDev X = sc_exp_view(*p, tmp->add(t.rows), tmp->add(t.src_idx), t.rows.size(), p->d_ids, d_src);
+    check_launch(launch_selcache_expand(X, (unsigned long long*)d_row_off, d_keys, d_proxy, cap_entries,
+                                        (unsigned long long*)d_total, st, e->cus),
+                 "selcache expand kernel launch");
+    fence(p->tab, st);
+    fence(tmp, st);
+  });
+}
+
+// Rows, offsets and (when they fit) entries back to the host after the
+// expansion queued on the handle's stream.
+static void sc_expand_copy_back(Engine& e, size_t n_rows, const DevMem& d_off, const DevMem& d_keys,
+                                const DevMem& d_proxy, uint64_t* row_off, cg_policy_key* keys, uint16_t* proxy,
+                                size_t cap, uint64_t* total) {
+  hipStream_t st = (hipStream_t)e.stream;
+  hip_check(hipMemcpyAsync(row_off, d_off.get(), (n_rows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st),
+            "hipMemcpy D2H");
+  dev_sync(e, nullptr);
+  const uint64_t n = row_off[n_rows];
+  if (total) *total = n;
+  if (n && n <= cap) {
+    hip_check(hipMemcpyAsync(keys, d_keys.get(), n * sizeof(cg_policy_key), hipMemcpyDeviceToHost, st), "hipMemcpy D2H");
+    hip_check(hipMemcpyAsync(proxy, d_proxy.get(), n * sizeof(uint16_t), hipMemcpyDeviceToHost, st), "hipMemcpy D2H");
+    dev_sync(e, nullptr);
+  }
+}
+
+int cg_selcache_expand_host(uint64_t h, uint32_t sc_id, const cg_expand_table* table, const uint64_t* src,
+                            size_t src_rows, uint64_t* row_off, cg_policy_key* keys, uint16_t* proxy,
+                            size_t cap_entries, uint64_t* total) {
+  return guarded([&] {
+    auto e = get(h);
+    e->require_gpu();
+    sc_check_expand_out(table, row_off, keys, proxy, cap_entries);
+    const auto p = sc_pub(*e, sc_id);
+    const ScExpTab t = sc_compile_expand(*table, src_rows);
+    const size_t src_bytes = src_rows * (size_t)p->idents->words * sizeof(uint64_t);
+    if (src_bytes && !src) fail(CG_INVALID_ARGUMENT, "selcache expand: NULL source matrix");
+    e->set_device();
+    DevTables tmp;
+    DevMem d_src, d_off, d_keys, d_proxy;
+    d_src.upload(src, src_bytes);
+    d_off.alloc((t.rows.size() + 1) * sizeof(uint64_t));
+    d_keys.alloc(cap_entries * sizeof(cg_policy_key));
+    d_proxy.alloc(cap_entries * sizeof(uint16_t));
+    const ScExpDev X = sc_exp_view(*p, tmp.add(t.rows), tmp.add(t.src_idx), t.rows.size(), p->d_ids, d_src.as<uint64_t>());
+    check_launch(launch_selcache_expand(X, d_off.as<unsigned long long>(), d_keys.get(), d_proxy.as<uint16_t>(),
+                                        cap_entries, nullptr, e->stream, e->cus),
+                 "selcache expand kernel launch");
+    fence(p->tab, e->stream);
+    sc_expand_copy_back(*e, t.rows.size(), d_off, d_keys, d_proxy, row_off, keys, proxy, cap_entries, total);
+  });
+}
+
+static void sc_check_entries_args(const ScPublished& p, const uint32_t* eps, size_t n, const void* flags) {
+  if (n && (!eps || !flags)) fail(CG_INVALID_ARGUMENT, "selcache entries: NULL endpoints/flags");
+  if (n > 0x3FFFFFFFu) fail(CG_MAP_FULL, "selcache entries: too many endpoints");
+  for (size_t i = 0; i < n; ++i)
+    if (eps[i] >= p.idents->n) fail(CG_INVALID_ARGUMENT, "selcache entries: endpoint index outside the identity table");
+}
+
+int cg_selcache_entries_host(uint64_t h, uint32_t sc_id, const cg_selector_table* sels, const uint32_t* endpoints,
+                             size_t n_endpoints, const cg_expand_table* table, uint64_t* row_off,
+                             cg_policy_key* keys, uint16_t* proxy, size_t cap_entries, uint64_t* total,
+                             uint8_t* flags) {
+  return guarded([&] {
+    auto e = get(h);
+    e->require_gpu();
+    sc_check_expand_out(table, row_off, keys, proxy, cap_entries);
+    const auto p = sc_pub(*e, sc_id);
+    sc_check_entries_args(*p, endpoints, n_endpoints, flags);
+    ScSelTab own;
+    if (sels) own = sc_compile_selectors(*p->idents, sc_parse_selectors(*sels));
+    const size_t S = own.sels.size(), E = n_endpoints, W = p->idents->words;
+    const ScExpTab t = sc_compile_expand(*table, S + 2 * E);
+    e->set_device();
+    DevTables tmp;
+    DevMem d_src, d_ep, d_fl, d_off, d_keys, d_proxy;
+    d_src.alloc((S + 2 * E) * W * sizeof(uint64_t));
+    d_off.alloc((t.rows.size() + 1) * sizeof(uint64_t));
+    d_keys.alloc(cap_entries * sizeof(cg_policy_key));
+    d_proxy.alloc(cap_entries * sizeof(uint16_t));
+    unsigned long long* src = d_src.as<unsigned long long>();
+    if (S)
+      check_launch(launch_selcache_match(p->dI, sc_upload_table(own, tmp), src, e->stream, e->cus),
+                   "selcache match kernel launch");
+    if (E) {
+      d_ep.upload(endpoints, E * sizeof(uint32_t));
+      d_fl.alloc(E);
+      check_launch(launch_selcache_reach(p->dR, p->idents->n, p->idents->words, d_ep.as<uint32_t>(), E, src + S * W,
+                                         src + (S + E) * W, d_fl.as<uint8_t>(), e->stream),
+                   "selcache reach kernel launch");
+      hip_check(hipMemcpyAsync(flags, d_fl.get(), E, hipMemcpyDeviceToHost, (hipStream_t)e->stream), "hipMemcpy D2H");
+    }
+    const ScExpDev X = sc_exp_view(*p, tmp.add(t.rows), tmp.add(t.src_idx), t.rows.size(), p->d_ids, d_src.as<uint64_t>());
+    check_launch(launch_selcache_expand(X, d_off.as<unsigned long long>(), d_keys.get(), d_proxy.as<uint16_t>(),
+                                        cap_entries, nullptr, e->stream, e->cus),
+                 "selcache expand kernel launch");
+    fence(p->tab, e->stream);
+    sc_expand_copy_back(*e, t.rows.size(), d_off, d_keys, d_proxy, row_off, keys, proxy, cap_entries, total);
+  });
+}
+
+int cg_diag_selcache_expand_host(uint64_t h, uint32_t sc_id, const cg_expand_table* table, const uint64_t* src,
+                                 size_t src_rows, uint64_t* row_off, cg_policy_key* keys, uint16_t* proxy,
+                                 size_t cap_entries, uint64_t* total, uint32_t threads) {
+  return guarded([&] {
+    auto e = get(h);
+    sc_check_expand_out(table, row_off, keys, proxy, cap_entries);
+    const auto p = sc_pub(*e, sc_id);
+    const ScExpTab t = sc_compile_expand(*table, src_rows);
+    if (src_rows * (size_t)p->idents->words && !src) fail(CG_INVALID_ARGUMENT, "selcache expand: NULL source matrix");
+    uint64_t n = 0;
+    sc_expand_host(sc_exp_view(*p, t.rows.data(), t.src_idx.data(), t.rows.size(), p->idents->ids.data(), src),
+                   row_off, keys, proxy, cap_entries, &n, threads);
+    if (total) *total = n;
+  });
+}
+
+int cg_diag_selcache_entries_host(uint64_t h, uint32_t sc_id, const cg_selector_table* sels,
+                                  const uint32_t* endpoints, size_t n_endpoints, const cg_expand_table* table,
+                                  uint64_t* row_off, cg_policy_key* keys, uint16_t* proxy, size_t cap_entries,
+                                  uint64_t* total, uint8_t* flags, uint32_t threads) {
+  return guarded([&] {
+    auto e = get(h);
+    sc_check_expand_out(table, row_off, keys, proxy, cap_entries);
+    const auto p = sc_pub(*e, sc_id);
+    sc_check_entries_args(*p, endpoints, n_endpoints, flags);
+    ScSelTab own;
+    if (sels) own = sc_compile_selectors(*p->idents, sc_parse_selectors(*sels));
+    const size_t S = own.sels.size(), E = n_endpoints, W = p->idents->words;
+    const ScExpTab t = sc_compile_expand(*table, S + 2 * E);
+    std::vector<uint64_t> src(std::max<size_t>((S + 2 * E) * W, 1), 0);
+    if (S) sc_match_host(p->idents->view(), own.view(), src.data(), threads);
+    if (E) {
+      sc_ensure_host_m(*e, *p, threads);
+      sc_reach_host(p->host_rules(), p->idents->n, p->idents->words, endpoints, E, src.data() + S * W,
+                    src.data() + (S + E) * W, flags, threads);
+    }
+    uint64_t n = 0;
+    sc_expand_host(sc_exp_view(*p, t.rows.data(), t.src_idx.data(), t.rows.size(), p->idents->ids.data(), src.data()),
+                   row_off, keys, proxy, cap_entries, &n, threads);
+    if (total) *total = n;
   });
 }
 

@@ -949,4 +949,35 @@ CG_HD inline bool sc_matches(const ScIdentDev& I, const ScSelDev& T, uint32_t s,
   return true;
 }
 
+// Expansion of bitset rows into policy-map entries (kernels_selcache.hip;
+// convertL4FilterToPolicyMapKeys, pkg/endpoint/policy.go:111-130;
+// computeDesiredL3PolicyMapEntries, :298-371).  Row r's set is the OR of its
+// source rows (all ones with kScExpAll), cut to the identities that exist.
+constexpr uint32_t kScExpAll = 1u;  // CG_EXP_ALL
+
+struct ScExpRow {
+  uint32_t src_beg, src_n;  // its source-row indices in ScExpDev.src_idx
+  uint32_t tmpl;            // second word of cg_policy_key: dport (network order) | protocol << 16 | egress << 24
+  uint16_t proxy_be;
+  uint16_t flags;
+};
+static_assert(sizeof(ScExpRow) == 16, "expansion row record");
+
+struct ScExpDev {
+  const ScExpRow* rows;
+  const uint32_t* src_idx;
+  const uint32_t* ids;            // n_ids identity numbers, in bit order
+  const unsigned long long* src;  // [src_rows][words]
+  uint32_t n_rows, n_ids, words;
+};
+
+// Word w of a row's set.  The last word's padding bits are cleared whatever
+// the source matrix holds there, so no set bit stands for an index >= n_ids.
+CG_HD inline unsigned long long sc_exp_word(const ScExpDev& X, const ScExpRow& row, uint32_t w) {
+  unsigned long long v = (row.flags & kScExpAll) ? ~0ull : 0ull;
+  for (uint32_t x = 0; x < row.src_n; ++x) v |= X.src[(size_t)X.src_idx[row.src_beg + x] * X.words + w];
+  const uint32_t tail = X.n_ids & 63u;
+  return (w == X.words - 1 && tail) ? v & ((1ull << tail) - 1ull) : v;
+}
+
 }  // namespace cg

@@ -108,5 +108,12 @@ int launch_selcache_match(const ScIdentDev& I, const ScSelDev& T, unsigned long 
 // index >= n_ids yields zero rows).  R.M is the rule selectors' match matrix.
 int launch_selcache_reach(const ScRuleDev& R, uint32_t n_ids, uint32_t words, const uint32_t* eps, size_t n,
                           unsigned long long* ing, unsigned long long* eg, uint8_t* flags, void* stream);
+// Expansion: count per row into row_off[0..R), exclusive scan in place to
+// row_off[0..R] (and *total when not NULL), then emit keys[total] / proxy[total]
+// unless total > cap.  keys is 8-byte aligned.  R = 0 runs the scan alone.
+int launch_selcache_expand(const ScExpDev& X, unsigned long long* row_off, void* keys, uint16_t* proxy,
+                           unsigned long long cap, unsigned long long* total, void* stream, int cus);
+// Words of a row one emit round of a block covers (one per lane).
+uint32_t selcache_expand_span();
 
 }  // namespace cg

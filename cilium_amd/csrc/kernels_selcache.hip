@@ -21,6 +21,23 @@
 // same in all lanes — and ORs the selected rules' allow rows and complemented
 // require rows at its word.  Both directions in one pass.  Bound by reading
 // rows of M, each read coalesced over the block's words.
+//
+// Expansion (convertL4FilterToPolicyMapKeys, pkg/endpoint/policy.go:111-130;
+// computeDesiredL4PolicyMapEntries, :144-193; computeDesiredL3PolicyMapEntries,
+// :298-371) turns bitset rows into policy-map entries in three launches.  A
+// row's set D[r] (sc_exp_word) is never stored: count and emit both recompute
+// it from the source rows, which for the common one-source row costs the same
+// read a stored D would, and spares an R x W workspace and its write.
+//   selcache_expand_count_kernel: one block per row, lanes stride the row's
+//     words (coalesced), popcount, block reduce: row_off[r] = |D[r]|.
+//   selcache_expand_scan_kernel: one block, exclusive 64-bit scan of the row
+//     counts in place with a carried running sum; no block waits on another.
+//   selcache_expand_emit_kernel: one block per row, a round covers kExpSpan
+//     words, one per lane.  A wave scan of the popcounts gives each word's
+//     base; then per non-zero word (read wave-uniformly) lane l tests bit l,
+//     ranks itself with mbcnt and writes its key and proxy port at base +
+//     rank: ascending bit order, whole lines, no atomics.  Wider rows take
+//     further rounds with the base carried.
 #include <hip/hip_runtime.h>
 
 #include "dev_types.h"
@@ -155,7 +172,148 @@ __global__ __launch_bounds__(kReachThreads) void selcache_reach_kernel(ScRuleDev
   if (blockIdx.x == 0 && threadIdx.x == 0) flags[ei] = (uint8_t)fl;
 }
 
+constexpr int kCountThreads = 256;
+constexpr int kScanThreads = 1024;
+constexpr int kExpThreads = 1024;            // 16 waves
+constexpr uint32_t kExpSpan = kExpThreads;   // words per emit round: one per lane
+static_assert(kCountThreads % 64 == 0 && kScanThreads % 64 == 0 && kExpThreads % 64 == 0, "whole waves");
+
+__global__ __launch_bounds__(kCountThreads) void selcache_expand_count_kernel(ScExpDev X,
+                                                                              unsigned long long* __restrict__ row_off) {
+  __shared__ uint32_t part[kCountThreads / 64];
+  for (uint32_t r = blockIdx.x; r < X.n_rows; r += gridDim.x) {
+    const ScExpRow row = X.rows[r];
+    uint32_t c = 0;  // at most n_ids < 2^32
+    for (uint32_t w = threadIdx.x; w < X.words; w += kCountThreads) c += (uint32_t)__popcll(sc_exp_word(X, row, w));
+    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d);
+    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long t = 0;
+      for (int k = 0; k < kCountThreads / 64; ++k) t += part[k];
+      row_off[r] = t;
+    }
+    __syncthreads();  // the next row overwrites the partial sums
+  }
+}
+
+// In place: row_off[i] holds row i's count on entry and the sum of the counts
+// before it on exit; row_off[n] (and *total) the sum of all.  Every element
+// is read and rewritten by the same thread.
+__global__ __launch_bounds__(kScanThreads) void selcache_expand_scan_kernel(unsigned long long* __restrict__ row_off,
+                                                                            uint32_t n,
+                                                                            unsigned long long* __restrict__ total) {
+  __shared__ unsigned long long wave_sum[kScanThreads / 64];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  unsigned long long carry = 0;
+  for (uint32_t i0 = 0; i0 < n; i0 += kScanThreads) {
+    const uint32_t i = i0 + threadIdx.x;
+    const unsigned long long v = i < n ? row_off[i] : 0ull;
+    unsigned long long incl = v;
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned long long t = __shfl_up(incl, d);
+      if (lane >= (uint32_t)d) incl += t;
+    }
+    if (lane == 63u) wave_sum[wave] = incl;
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+    for (uint32_t k = 0; k < kScanThreads / 64; ++k) {
+      const unsigned long long s = wave_sum[k];
+      before += k < wave ? s : 0ull;
+      all += s;
+    }
+    __syncthreads();  // the next chunk overwrites the wave sums
+    if (i < n) row_off[i] = carry + before + incl - v;
+    carry += all;
+  }
+  if (threadIdx.x == 0) {
+    row_off[n] = carry;
+    if (total) *total = carry;
+  }
+}
+
+__device__ __forceinline__ unsigned long long lane64(unsigned long long v, uint32_t j) {  // j wave-uniform
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)j);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)j);
+  return (unsigned long long)lo | ((unsigned long long)hi << 32);
+}
+
+__global__ __launch_bounds__(kExpThreads) void selcache_expand_emit_kernel(ScExpDev X,
+                                                                           const unsigned long long* __restrict__ row_off,
+                                                                           unsigned long long cap, uint2* __restrict__ keys,
+                                                                           uint16_t* __restrict__ proxy) {
+  __shared__ uint32_t wave_sum[kExpThreads / 64];
+  if (row_off[X.n_rows] > cap) return;  // the same value in every block: the buffers stay untouched
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  for (uint32_t r = blockIdx.x; r < X.n_rows; r += gridDim.x) {
+    unsigned long long base = row_off[r];
+    const unsigned long long end = row_off[r + 1];
+    if (end == base) continue;  // an empty row, for the whole block
+    const ScExpRow row = X.rows[r];
+    for (uint32_t w0 = 0; w0 < X.words; w0 += kExpSpan) {
+      const uint32_t w = w0 + threadIdx.x;
+      const unsigned long long word = w < X.words ? sc_exp_word(X, row, w) : 0ull;
+      const uint32_t cnt = (uint32_t)__popcll(word);
+      uint32_t incl = cnt;
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(incl, d);
+        if (lane >= (uint32_t)d) incl += t;
+      }
+      if (lane == 63u) wave_sum[wave] = incl;
+      __syncthreads();
+      uint32_t before = 0, all = 0;
+      for (uint32_t k = 0; k < kExpThreads / 64; ++k) {
+        const uint32_t s = wave_sum[k];
+        before += k < wave ? s : 0u;
+        all += s;
+      }
+      __syncthreads();  // the next round overwrites the wave sums
+      const unsigned long long mine = base + before + (incl - cnt);  // where this lane's word starts
+      unsigned long long nz = __ballot(word != 0ull);
+      while (nz) {
+        const uint32_t j = (uint32_t)__builtin_ctzll(nz);
+        nz &= nz - 1;
+        const unsigned long long wj = lane64(word, j);
+        const unsigned long long bj = lane64(mine, j);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(wj >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wj, 0u));
+        const unsigned long long at = bj + rank;
+        // sc_exp_word cleared the padding bits, so the identity index is < n_ids;
+        // `at < end` holds when count and emit saw the same source matrix
+        if (((wj >> lane) & 1ull) && at < end) {
+          const uint32_t ident = (w0 + (wave << 6) + j) * 64u + lane;
+          keys[at] = make_uint2(X.ids[ident], row.tmpl);
+          proxy[at] = row.proxy_be;
+        }
+      }
+      base += all;
+    }
+  }
+}
+
 }  // namespace
+
+uint32_t selcache_expand_span() { return kExpSpan; }
+
+int launch_selcache_expand(const ScExpDev& X, unsigned long long* row_off, void* keys, uint16_t* proxy,
+                           unsigned long long cap, unsigned long long* total, void* stream, int cus) {
+  const hipStream_t st = (hipStream_t)stream;
+  const uint32_t per_cu = (uint32_t)(cus > 0 ? cus : 1);
+  int err;
+  if (X.n_rows) {
+    const uint32_t g = X.n_rows < 8u * per_cu ? X.n_rows : 8u * per_cu;
+    hipLaunchKernelGGL(selcache_expand_count_kernel, dim3(g), dim3(kCountThreads), 0, st, X, row_off);
+    if ((err = (int)hipGetLastError())) return err;
+  }
+  hipLaunchKernelGGL(selcache_expand_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, row_off, X.n_rows, total);
+  if ((err = (int)hipGetLastError())) return err;
+  if (X.n_rows && X.words && cap) {
+    const uint32_t g = X.n_rows < 4u * per_cu ? X.n_rows : 4u * per_cu;
+    hipLaunchKernelGGL(selcache_expand_emit_kernel, dim3(g), dim3(kExpThreads), 0, st, X, row_off, cap, (uint2*)keys,
+                       proxy);
+    if ((err = (int)hipGetLastError())) return err;
+  }
+  return 0;
+}
 
 int launch_selcache_match(const ScIdentDev& I, const ScSelDev& T, unsigned long long* bits, void* stream, int cus) {
   if (I.n == 0 || T.n == 0) return 0;

@@ -94,10 +94,12 @@ void PolicyMapState::read_counters(Engine& e, uint32_t id, uint64_t* pk, uint64_
   *by = v[1];
 }
 
-void PolicyMapState::zero_counter(Engine& e, uint32_t id) {
-  if (!e.has_gpu() || !d_counters) return;
+void PolicyMapState::zero_counter(Engine& e, uint32_t id) { zero_counters(e, id, 1); }
+
+void PolicyMapState::zero_counters(Engine& e, uint32_t first_id, uint32_t count) {
+  if (!e.has_gpu() || !d_counters || !count) return;
   e.set_device();
-  hip_check(hipMemset(d_counters->as<uint64_t>() + (size_t)id * 2, 0, 16), "zero counter");
+  hip_check(hipMemset(d_counters->as<uint64_t>() + (size_t)first_id * 2, 0, (size_t)count * 16), "zero counter");
 }
 
 }  // namespace cg

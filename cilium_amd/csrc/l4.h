@@ -47,6 +47,7 @@ struct PolicyMapState {
   void rebuild(Engine& e);  // cuckoo build + upload (counters preserved by id)
   void read_counters(Engine& e, uint32_t id, uint64_t* pk, uint64_t* by);
   void zero_counter(Engine& e, uint32_t id);
+  void zero_counters(Engine& e, uint32_t first_id, uint32_t count);  // a run of consecutive slots
 };
 
 }  // namespace cg

@@ -260,6 +260,67 @@ void sc_reach_host(const ScRuleDev& R, uint32_t n_ids, uint32_t words, const uin
   });
 }
 
+ScExpTab sc_compile_expand(const cg_expand_table& t, size_t src_rows) {
+  ScExpTab out;
+  const size_t n = t.n_rows;
+  if (n == 0) return out;
+  if (n > 0x7FFFFFFFu) fail(CG_MAP_FULL, "expansion table: too many rows");
+  if (!t.rows || !t.src_off) fail(CG_INVALID_ARGUMENT, "expansion table: NULL rows/src_off");
+  check_off32(t.src_off, n, "expansion sources");
+  const size_t m = t.src_off[n];
+  if (m && !t.src_idx) fail(CG_INVALID_ARGUMENT, "expansion table: NULL src_idx");
+  for (size_t x = 0; x < m; ++x)
+    if (t.src_idx[x] >= src_rows) fail(CG_INVALID_ARGUMENT, "expansion table: source row index out of range");
+  out.rows.resize(n);
+  for (size_t r = 0; r < n; ++r) {
+    const cg_expand_row& in = t.rows[r];
+    if (in.flags & ~(uint32_t)CG_EXP_ALL) fail(CG_INVALID_ARGUMENT, "expansion table: unknown row flags");
+    out.rows[r] = ScExpRow{t.src_off[r], t.src_off[r + 1] - t.src_off[r],
+                           (uint32_t)in.dport | ((uint32_t)in.protocol << 16) | ((uint32_t)in.egress << 24),
+                           in.proxy_port, (uint16_t)in.flags};
+  }
+  if (m) out.src_idx.assign(t.src_idx, t.src_idx + m);
+  return out;
+}
+
+void sc_expand_host(const ScExpDev& X, uint64_t* row_off, cg_policy_key* keys, uint16_t* proxy, uint64_t cap,
+                    uint64_t* total, uint32_t threads) {
+  const size_t R = X.n_rows;
+  std::vector<uint64_t> cnt(R, 0);
+  run_threads(R, threads, [&](size_t lo, size_t hi) {
+    for (size_t r = lo; r < hi; ++r)
+      for (uint32_t w = 0; w < X.words; ++w) cnt[r] += (uint64_t)__builtin_popcountll(sc_exp_word(X, X.rows[r], w));
+  });
+  uint64_t sum = 0;
+  for (size_t r = 0; r < R; ++r) {
+    row_off[r] = sum;
+    sum += cnt[r];
+  }
+  row_off[R] = sum;
+  *total = sum;
+  if (sum > cap) return;
+  run_threads(R, threads, [&](size_t lo, size_t hi) {
+    for (size_t r = lo; r < hi; ++r) {
+      const ScExpRow& row = X.rows[r];
+      uint64_t at = row_off[r];
+      for (uint32_t w = 0; w < X.words; ++w) {
+        uint64_t word = sc_exp_word(X, row, w);
+        while (word) {
+          const uint32_t b = (uint32_t)__builtin_ctzll(word);
+          word &= word - 1;
+          cg_policy_key k;
+          k.sec_label = X.ids[64u * w + b];
+          k.dport = (uint16_t)row.tmpl;
+          k.protocol = (uint8_t)(row.tmpl >> 16);
+          k.egress = (uint8_t)(row.tmpl >> 24);
+          keys[at] = k;
+          proxy[at++] = row.proxy_be;
+        }
+      }
+    }
+  });
+}
+
 ScRuleDev ScPublished::host_rules() const {
   ScRuleDev r{};
   r.subject = rules->subject.data();
@@ -288,6 +349,7 @@ void SelcacheState::rebuild(Engine& e) {
     e.set_device();
     auto tab = std::make_shared<DevTables>();
     p->dI = ScIdentDev{tab->add(idents->lab_off), tab->add(idents->labels), idents->n, idents->words};
+    p->d_ids = tab->add(idents->ids);
     p->dT = ScSelDev{tab->add(p->seltab.sels), tab->add(p->seltab.reqs), tab->add(p->seltab.vals),
                      (uint32_t)p->seltab.sels.size()};
     ScRuleDev r{};

@@ -71,6 +71,19 @@ void sc_match_host(const ScIdentDev& I, const ScSelDev& T, uint64_t* bits, uint3
 void sc_reach_host(const ScRuleDev& R, uint32_t n_ids, uint32_t words, const uint32_t* eps, size_t n, uint64_t* ing,
                    uint64_t* eg, uint8_t* flags, uint32_t threads);
 
+// A cg_expand_table compiled to device records (dev_types.h ScExpRow).
+struct ScExpTab {
+  std::vector<ScExpRow> rows;
+  std::vector<uint32_t> src_idx;
+};
+// Validates offsets and that every source index is < src_rows
+// (CG_INVALID_ARGUMENT otherwise).
+ScExpTab sc_compile_expand(const cg_expand_table& t, size_t src_rows);
+// What the three expansion kernels compute: row_off[R + 1], *total, and —
+// unless *total > cap — keys[*total] / proxy[*total], rows on `threads` threads.
+void sc_expand_host(const ScExpDev& X, uint64_t* row_off, cg_policy_key* keys, uint16_t* proxy, uint64_t cap,
+                    uint64_t* total, uint32_t threads);
+
 // One published build: the host tables and, on a GPU handle, their device
 // copies with the rule selectors' match matrix M already computed.
 struct ScPublished {
@@ -82,6 +95,7 @@ struct ScPublished {
   ScIdentDev dI{};
   ScSelDev dT{};
   ScRuleDev dR{};
+  const uint32_t* d_ids = nullptr;  // idents->ids on the device: what expansion writes as sec_label
   ScRuleDev host_rules() const;   // over host_m
 };
 

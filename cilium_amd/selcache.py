@@ -10,6 +10,10 @@ kernels over the whole identity cache:
   launch for all selectors (``cg_selcache_match_*``);
 * ``reach(endpoint_ids)``: per endpoint the ingress / egress allow-bitsets
   over all identities and the enforcement flags (``cg_selcache_reach_*``);
+* ``expand`` / ``endpoint_policy_map_entries`` / ``sync_policy_maps``: the
+  bitsets expanded into raw policy-map entries by three more kernels
+  (``cg_selcache_expand_*``, ``cg_selcache_entries_host``) and applied with
+  one ``PolicyMap.sync`` per map — no Python object per entry;
 * ``endpoint_policy_map_states``: the dicts ``resolve.endpoint_policy_map_state``
   returns, for many endpoints at once.
 
@@ -26,7 +30,8 @@ import numpy as np
 
 from . import _native as N
 from . import resolve as R
-from .policy import PolicyKey, TrafficDirection
+from .classifier import POLICY_KEY_DTYPE
+from .policy import PolicyKey, TrafficDirection, htons
 
 _OPS = {"In": N.CG_SEL_IN, "NotIn": N.CG_SEL_NOT_IN, "Exists": N.CG_SEL_EXISTS,
         "DoesNotExist": N.CG_SEL_DOES_NOT_EXIST}
@@ -95,6 +100,28 @@ def unpack_rows(bits: np.ndarray, n: int) -> np.ndarray:
     return np.unpackbits(bits.view(np.uint8).reshape(rows, -1), axis=1, bitorder="little")[:, :n].astype(bool)
 
 
+EXPAND_ROW_DTYPE = np.dtype([("dport", "<u2"), ("protocol", "u1"), ("egress", "u1"), ("proxy_port", "<u2"),
+                             ("flags", "<u2")])
+
+
+class ExpandTable:
+    """A cg_expand_table built from rows (dport_be, protocol, egress,
+    proxy_port_be, flags, [source row indices]); dport and proxy port in
+    network byte order, as the policy map stores them.  Its arrays are kept
+    alive by this object."""
+
+    def __init__(self, rows: Sequence[tuple]):
+        self.n = len(rows)
+        self.rows = np.zeros(max(self.n, 1), EXPAND_ROW_DTYPE)
+        for i, r in enumerate(rows):
+            self.rows[i] = tuple(r[:5])
+        self.src_off, self.src_idx = _csr([list(r[5]) for r in rows])
+        self.c = N.ExpandTableC(self.n, _p(self.rows), _p(self.src_off), _p(self.src_idx))
+
+    def ref(self):
+        return C.byref(self.c)
+
+
 class SelectorCache:
     """The identity cache and a repository's selectors on the device."""
 
@@ -108,6 +135,7 @@ class SelectorCache:
         self._index: dict[int, int] = {}
         self.repo: Optional[R.Repository] = None
         self.words = 0
+        self._entries_cap = 1 << 16             # entries() starts its buffers here and grows them
 
     def destroy(self) -> None:
         N.check(N.lib.cg_selcache_destroy(self.cl.h, self.id))
@@ -248,7 +276,163 @@ class SelectorCache:
         N.check(N.lib.cg_selcache_reach_dev(self.cl.h, self.id, _p(d_endpoints), n, _p(d_ing), _p(d_eg),
                                             _p(d_flags), stream))
 
+    # ------------------------------------------------------------ expand --
+    def expand_into(self, table: ExpandTable, src: np.ndarray, keys: np.ndarray, proxy_be: np.ndarray,
+                    diag_cpu: bool = False, threads: int = 1) -> tuple[np.ndarray, int]:
+        """Expand `table`'s rows over the source matrix src[rows][W] (u64, the
+        layout of match / reach) into the caller's keys (POLICY_KEY_DTYPE) and
+        proxy_be (u16) arrays, whose common length is the capacity.  Returns
+        (row_off[R + 1], total); when total exceeds the capacity the arrays
+        are left untouched and row_off is still valid.  Row r owns
+        [row_off[r], row_off[r+1]), in ascending bit order."""
+        src = np.ascontiguousarray(src, np.uint64)
+        src_rows = src.shape[0] if src.ndim == 2 else (src.size // self.words if self.words else 0)
+        if src.size != src_rows * self.words:
+            raise ValueError("src is not rows x W words")
+        if keys.dtype != POLICY_KEY_DTYPE or proxy_be.dtype != np.uint16 or len(keys) != len(proxy_be) \
+                or not keys.flags.c_contiguous or not proxy_be.flags.c_contiguous:
+            raise ValueError("keys / proxy_be: contiguous POLICY_KEY_DTYPE and uint16 arrays of one length")
+        row_off = np.zeros(table.n + 1, np.uint64)
+        total = C.c_uint64()
+        cap = len(keys)
+        args = (self.cl.h, self.id, table.ref(), _p(src) if src.size else None, src_rows, _p(row_off),
+                _p(keys) if cap else None, _p(proxy_be) if cap else None, cap, C.byref(total))
+        if diag_cpu:
+            N.check(N.lib.cg_diag_selcache_expand_host(*args, threads))
+        else:
+            N.check(N.lib.cg_selcache_expand_host(*args))
+        return row_off, int(total.value)
+
+    def expand(self, table: ExpandTable, src: np.ndarray, diag_cpu: bool = False, threads: int = 1):
+        """(row_off, keys, proxy_be) of expand_into, sized by a first call
+        with no capacity."""
+        none = (np.zeros(0, POLICY_KEY_DTYPE), np.zeros(0, np.uint16))
+        row_off, total = self.expand_into(table, src, *none, diag_cpu=diag_cpu, threads=threads)
+        if total == 0:
+            return (row_off, *none)
+        keys, proxy = np.zeros(total, POLICY_KEY_DTYPE), np.zeros(total, np.uint16)
+        row_off, _ = self.expand_into(table, src, keys, proxy, diag_cpu=diag_cpu, threads=threads)
+        return row_off, keys, proxy
+
+    def expand_dev(self, table: ExpandTable, d_src, src_rows: int, d_row_off, d_keys, d_proxy, cap_entries: int,
+                   d_total=None, stream=None) -> None:
+        """expand_into() on device tensors, on `stream`: d_src src_rows * W
+        words, d_row_off R + 1 words, d_keys cap_entries 8-byte keys, d_proxy
+        cap_entries u16, d_total one word (or None).  The table is a host
+        table."""
+        N.check(N.lib.cg_selcache_expand_dev(self.cl.h, self.id, table.ref(), _p(d_src), src_rows, _p(d_row_off),
+                                             _p(d_keys), _p(d_proxy), cap_entries, _p(d_total), stream))
+
+    def entries(self, selectors: Optional[Sequence[R.EndpointSelector]], eps: np.ndarray, table: ExpandTable,
+                diag_cpu: bool = False, threads: int = 1):
+        """The fused call (cg_selcache_entries_host): `table`'s rows over the
+        source matrix [selectors' match rows | eps' ingress reach rows | eps'
+        egress reach rows].  Returns (row_off, keys, proxy_be, flags).  The
+        entry buffers start at the last call's size and the call is repeated
+        once when the result does not fit."""
+        eps = np.ascontiguousarray(eps, np.uint32).reshape(-1)
+        tab = _SelectorTable(selectors) if selectors else None
+        row_off = np.zeros(table.n + 1, np.uint64)
+        flags = np.zeros(max(len(eps), 1), np.uint8)
+        total = C.c_uint64()
+        cap = self._entries_cap
+        while True:
+            keys, proxy = np.zeros(max(cap, 1), POLICY_KEY_DTYPE), np.zeros(max(cap, 1), np.uint16)
+            args = (self.cl.h, self.id, None if tab is None else tab.ref(), _p(eps) if len(eps) else None, len(eps),
+                    table.ref(), _p(row_off), _p(keys), _p(proxy), cap, C.byref(total), _p(flags))
+            if diag_cpu:
+                N.check(N.lib.cg_diag_selcache_entries_host(*args, threads))
+            else:
+                N.check(N.lib.cg_selcache_entries_host(*args))
+            if total.value <= cap:
+                break
+            cap = int(total.value)
+        self._entries_cap = max(self._entries_cap, cap)
+        return row_off, keys[:total.value], proxy[:total.value], flags[:len(eps)]
+
     # -------------------------------------------------- endpoint policy --
+    def endpoint_policy_map_entries(self, endpoint_ids: Iterable[int],
+                                    redirect_ports: Optional[Mapping[tuple, int]] = None,
+                                    diag_cpu: bool = False, threads: int = 1) -> list[tuple[np.ndarray, np.ndarray]]:
+        """Per endpoint identity the raw policy-map entries (keys:
+        POLICY_KEY_DTYPE, proxy_be: uint16; network byte order) of
+        resolve.endpoint_policy_map_state, without a Python object per entry.
+        Each L4 filter is one expansion row over its selectors and each
+        direction one L3 row — the endpoint's reach row, or every identity
+        when the direction is not enforced (policy.go:144-193, :298-371) — and
+        all endpoints' rows go through one fused library call.  L4 resolution
+        and ComputePolicyEnforcement stay in resolve.py (per endpoint, they
+        do not scale with the identity count); the library's enforcement
+        flags are checked against that decision.  The localhost / world keys
+        (policy.go:267-296) are appended on the host and may repeat an L3
+        key; PolicyMap.sync takes the last."""
+        repo = self.repo
+        if repo is None:
+            raise ValueError("set_repository first")
+        endpoint_ids = [int(e) for e in endpoint_ids]
+        eps = self._endpoint_indices(endpoint_ids)
+        redirect_ports = redirect_ports or {}
+        sel_index: dict[R.EndpointSelector, int] = {}
+        per_ep = []
+        for e in endpoint_ids:
+            labels = self.identity_cache[e]
+            ing_on, eg_on = R.compute_policy_enforcement(repo, labels)
+            l4 = R.L4Policy(Ingress=repo.resolve_l4_ingress_policy(labels) if ing_on else {},
+                            Egress=repo.resolve_l4_egress_policy(labels) if eg_on else {})
+            l4_rows = []
+            # computeDesiredL4PolicyMapEntries (policy.go:144-193)
+            for filters, direction in ((l4.Ingress, TrafficDirection.Ingress), (l4.Egress, TrafficDirection.Egress)):
+                for f in filters.values():
+                    proxy = 0
+                    if f.is_redirect():
+                        proxy = int(redirect_ports.get((f.Ingress, f.Protocol, f.Port), 0))
+                        if proxy == 0:
+                            continue
+                    l4_rows.append((htons(f.Port & 0xFFFF), f.U8Proto, int(direction), htons(proxy), 0,
+                                    [sel_index.setdefault(s, len(sel_index)) for s in f.Endpoints]))
+            extra: dict[PolicyKey, int] = {}
+            R.determine_allow_localhost(extra, l4, repo.cfg.always_allow_localhost)
+            R.determine_allow_from_world(extra, repo.cfg.host_allows_world)
+            per_ep.append((ing_on, eg_on, l4_rows, extra))
+        S, E = len(sel_index), len(endpoint_ids)
+        rows, first = [], [0]
+        for n, (ing_on, eg_on, l4_rows, _) in enumerate(per_ep):
+            rows += l4_rows
+            rows.append((0, 0, int(TrafficDirection.Ingress), 0, 0, [S + n]) if ing_on
+                        else (0, 0, int(TrafficDirection.Ingress), 0, N.CG_EXP_ALL, []))
+            rows.append((0, 0, int(TrafficDirection.Egress), 0, 0, [S + E + n]) if eg_on
+                        else (0, 0, int(TrafficDirection.Egress), 0, N.CG_EXP_ALL, []))
+            first.append(len(rows))
+        row_off, keys, proxy, flags = self.entries(list(sel_index), eps, ExpandTable(rows), diag_cpu, threads)
+        if repo.cfg.enforcement == "default":
+            for e, fl, (ing_on, eg_on, _, _) in zip(endpoint_ids, flags, per_ep):
+                if "reserved:init" not in self.identity_cache[e] and (bool(fl & 1), bool(fl & 2)) != (ing_on, eg_on):
+                    raise RuntimeError(f"endpoint {e}: the library's enforcement flags {int(fl)} disagree with "
+                                       "resolve.compute_policy_enforcement")
+        out = []
+        for n, (_, _, _, extra) in enumerate(per_ep):
+            lo, hi = int(row_off[first[n]]), int(row_off[first[n + 1]])
+            k, p = keys[lo:hi], proxy[lo:hi]
+            if extra:
+                xk = np.zeros(len(extra), POLICY_KEY_DTYPE)
+                for i, key in enumerate(extra):
+                    xk[i] = (key.Identity, htons(key.DestPort), key.Nexthdr, key.TrafficDirection)
+                k = np.concatenate([k, xk])
+                p = np.concatenate([p, np.asarray([htons(v) for v in extra.values()], np.uint16)])
+            out.append((k, p))
+        return out
+
+    def sync_policy_maps(self, endpoint_ids: Iterable[int], maps: Sequence,
+                         redirect_ports: Optional[Mapping[tuple, int]] = None) -> list[tuple[int, int]]:
+        """Bring maps[i] (a PolicyMap) to endpoint i's desired state: one
+        fused expansion for all endpoints, then one PolicyMap.sync per map.
+        Returns the (added, deleted) counts per map."""
+        endpoint_ids = list(endpoint_ids)
+        if len(maps) != len(endpoint_ids):
+            raise ValueError("one map per endpoint")
+        ents = self.endpoint_policy_map_entries(endpoint_ids, redirect_ports)
+        return [pm.sync(k, p) for pm, (k, p) in zip(maps, ents)]
+
     def endpoint_policy_map_states(self, endpoint_ids: Iterable[int],
                                    redirect_ports: Optional[Mapping[tuple, int]] = None,
                                    diag_cpu: bool = False) -> list[dict]:

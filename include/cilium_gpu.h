@@ -813,6 +813,66 @@ int cg_selcache_reach_dev(uint64_t h, uint32_t sc_id, const uint32_t* d_endpoint
 int cg_selcache_reach_host(uint64_t h, uint32_t sc_id, const uint32_t* endpoints, size_t n, uint64_t* ing,
                            uint64_t* eg, uint8_t* flags);
 
+/* Expansion of bitset rows into policy-map entries: the identity loops of
+ * convertL4FilterToPolicyMapKeys (pkg/endpoint/policy.go:111-130),
+ * computeDesiredL4PolicyMapEntries (:144-193) and
+ * computeDesiredL3PolicyMapEntries (:298-371) over a source matrix
+ * src[src_rows][W] in the layout of the match / reach results. */
+#define CG_EXP_ALL 0x1u /* the row holds every identity (an unenforced direction, policy.go:311-313,343-345) */
+/* One expansion row: the policy-map key every entry of the row shares
+ * (policymap.go:64-69) and its value's proxy port (policymap.go:73-80). */
+typedef struct {
+  uint16_t dport;       /* network byte order */
+  uint8_t protocol;
+  uint8_t egress;
+  uint16_t proxy_port;  /* network byte order */
+  uint16_t flags;       /* CG_EXP_* */
+} cg_expand_row;
+/* Row r's identity set is the OR of the source rows
+ * src_idx[src_off[r] .. src_off[r+1]) — every identity with CG_EXP_ALL, none
+ * for an empty list without it — restricted to the identities that exist
+ * (padding bits of the source matrix are ignored). */
+typedef struct {
+  size_t n_rows;
+  const cg_expand_row* rows;
+  const uint32_t* src_off;  /* n_rows + 1 */
+  const uint32_t* src_idx;
+} cg_expand_table;
+/* row_off[n_rows + 1]: row r owns the entries [row_off[r], row_off[r+1]), in
+ * ascending bit order; keys[k].sec_label is the identity number of the bit,
+ * the rest of the key and proxy[k] are the row's.  *total (may be NULL in
+ * the _dev variant) = row_off[n_rows].  When *total > cap_entries, keys and
+ * proxy are left untouched and row_off is still valid, so cap_entries = 0
+ * sizes the buffers as cg_policymap_dump does.  table is a HOST table in all
+ * variants; a source index >= src_rows is CG_INVALID_ARGUMENT.
+ * _dev: device pointers (d_keys 8-byte aligned), asynchronous on stream. */
+int cg_selcache_expand_dev(uint64_t h, uint32_t sc_id, const cg_expand_table* table, const uint64_t* d_src,
+                           size_t src_rows, uint64_t* d_row_off, cg_policy_key* d_keys, uint16_t* d_proxy,
+                           size_t cap_entries, uint64_t* d_total, void* stream);
+int cg_selcache_expand_host(uint64_t h, uint32_t sc_id, const cg_expand_table* table, const uint64_t* src,
+                            size_t src_rows, uint64_t* row_off, cg_policy_key* keys, uint16_t* proxy,
+                            size_t cap_entries, uint64_t* total);
+/* The fused regeneration step (computeDesiredPolicyMapState's identity
+ * loops, policy.go:144-193 and :298-371): match, reach, expansion and one
+ * copy back on the handle's stream.  The source matrix is sels' match rows
+ * (S of them; sels may be NULL, S = 0), then the endpoints' ingress reach
+ * rows (n_endpoints), then their egress reach rows.  flags[n_endpoints] are
+ * the enforcement flags of cg_selcache_reach_host. */
+int cg_selcache_entries_host(uint64_t h, uint32_t sc_id, const cg_selector_table* sels, const uint32_t* endpoints,
+                             size_t n_endpoints, const cg_expand_table* table, uint64_t* row_off,
+                             cg_policy_key* keys, uint16_t* proxy, size_t cap_entries, uint64_t* total,
+                             uint8_t* flags);
+
+/* syncPolicyMap (pkg/endpoint/endpoint.go:2621-2701) as one update: the map
+ * holds exactly the given entries afterwards.  Keys absent from the list are
+ * deleted (*deleted); keys that are new or whose proxy port differs are
+ * written (*added); surviving keys keep their counters; a key given twice
+ * takes its last value.  All or nothing: more distinct keys than max_entries
+ * is CG_MAP_FULL and the map is unchanged.  One table rebuild and one
+ * publish, at the next verdict call.  added / deleted may be NULL. */
+int cg_policymap_sync(uint64_t h, uint32_t map_id, const cg_policy_key* keys, const uint16_t* proxy_ports_be,
+                      size_t n, size_t* added, size_t* deleted);
+
 /* ======================================================================== */
 /* Diagnostics (CPU test-suite only; no verdict entry point calls these)    */
 /* ======================================================================== */
@@ -850,6 +910,16 @@ int cg_diag_selcache_match_host(uint64_t h, uint32_t sc_id, const cg_selector_ta
                                 size_t cap_words, uint32_t threads);
 int cg_diag_selcache_reach_host(uint64_t h, uint32_t sc_id, const uint32_t* endpoints, size_t n, uint64_t* ing,
                                 uint64_t* eg, uint8_t* flags, uint32_t threads);
+/* cg_selcache_expand_host / cg_selcache_entries_host from the host walkers
+ * (the identity loops of policy.go:111-130, :144-193, :298-371 over the
+ * compiled tables); same arguments and results. */
+int cg_diag_selcache_expand_host(uint64_t h, uint32_t sc_id, const cg_expand_table* table, const uint64_t* src,
+                                 size_t src_rows, uint64_t* row_off, cg_policy_key* keys, uint16_t* proxy,
+                                 size_t cap_entries, uint64_t* total, uint32_t threads);
+int cg_diag_selcache_entries_host(uint64_t h, uint32_t sc_id, const cg_selector_table* sels,
+                                  const uint32_t* endpoints, size_t n_endpoints, const cg_expand_table* table,
+                                  uint64_t* row_off, cg_policy_key* keys, uint16_t* proxy, size_t cap_entries,
+                                  uint64_t* total, uint8_t* flags, uint32_t threads);
 
 #ifdef __cplusplus
 }

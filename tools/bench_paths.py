@@ -9,7 +9,8 @@ configs, one JSON line each (bench.py covers config 5, the 10K-rule HTTP set):
 * proxylib r2d2: 512 r2d2 rules over 64 ports, ~100M requests
   on the HTTP kernel
 * selcache (opt-in, --paths selcache): selector x identity matching and L3
-  reach, 65,536 identities, a 10,000-rule repository, 256 endpoints
+  reach, 65,536 identities, a 10,000-rule repository, 256 endpoints, and the
+  expansion of those bitsets into policy-map entries
 
 Inputs are resident in HBM before timing; kernels are timed with HIP events
 on their stream.  Each line carries the kernel's HBM roofline (algorithmic
@@ -733,12 +734,97 @@ def bench_cassandra(torch, dev, stream, cl, args, threads):
                                   400)
 
 
+def bench_selcache_expand(torch, dev, stream, sc, repo, eps, rule_m, args, threads):
+    """Expansion of the bench's bitsets into policy-map entries: per endpoint
+    its two L3 rows (the ingress / egress reach rows) and L4_ROWS rows over
+    two rule selectors each, drawn from the POOL rule selectors whose sets are
+    nearest L4_SET identities (a policy map holds at most 16,384 entries, so
+    L4 rows are sparse).  Checked against the host walker (cg_diag_selcache_entries_host
+    on `threads` threads, also the CPU leg), then timed: HIP events around
+    the three expansion kernels over a device source matrix, and the fused
+    call's wall time with its copy back.  The parent commit's
+    endpoint_policy_map_states runs on a sample of endpoints (its own L4 rows:
+    the repository's resolved filters) and is extrapolated."""
+    from cilium_amd.classifier import POLICY_KEY_DTYPE
+    from cilium_amd.policy import htons
+    from cilium_amd.selcache import ExpandTable
+    POOL, L4_ROWS, L4_SET = 64, 4, 1024
+    E, W = len(eps), sc.words
+    rng = np.random.default_rng(0xE7)
+    sels = sc.compile_repository(repo)[0]
+    bits_of_byte = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)
+    pop = bits_of_byte[np.ascontiguousarray(rule_m).view(np.uint8)].sum(axis=1, dtype=np.int64)
+    order = [int(i) for i in np.argsort(np.abs(pop - L4_SET), kind="stable")[:POOL]]
+    pool = [sels[i] for i in order]
+    S = len(pool)
+    rows = []
+    for n in range(E):
+        for k in range(L4_ROWS):
+            rows.append((htons(80 + k), 6, k & 1, htons(15001) if k == 0 else 0, 0,
+                         [int(x) for x in rng.choice(S, 2, replace=False)]))
+        rows.append((0, 0, 0, 0, 0, [S + n]))
+        rows.append((0, 0, 1, 0, 0, [S + E + n]))
+    table = ExpandTable(rows)
+    R = len(rows)
+    # ---- the fused call, checked against the host walker
+    sc.entries(pool, eps, table)  # sizes the entry buffers
+    fused = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        got = sc.entries(pool, eps, table)
+        fused.append(time.perf_counter() - t0)
+    sc.entries(pool, eps[:1], ExpandTable(rows[:1]), diag_cpu=True, threads=threads)  # the walker's own M, not timed
+    t0 = time.perf_counter()
+    want = sc.entries(pool, eps, table, diag_cpu=True, threads=threads)
+    walker_s = time.perf_counter() - t0
+    assert all(np.array_equal(a, b) for a, b in zip(got, want)), "selcache expand differs from the host walker"
+    total = len(got[1])
+    # ---- the three kernels over a device source matrix
+    d_src = torch.empty((S + 2 * E) * W, dtype=torch.int64, device=dev)
+    d_ep = torch.from_numpy(eps.view(np.int32)).to(dev)
+    d_fl = torch.empty(E, dtype=torch.uint8, device=dev)
+    d_off = torch.empty(R + 1, dtype=torch.int64, device=dev)
+    d_keys = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+    d_proxy = torch.empty(max(total, 1), dtype=torch.int16, device=dev)
+    d_total = torch.empty(1, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    sc.match_dev(pool, d_src[:S * W], stream=stream.cuda_stream)
+    sc.reach_dev(d_ep, E, d_src[S * W:(S + E) * W], d_src[(S + E) * W:], d_fl, stream=stream.cuda_stream)
+    expand_s = timed(torch, stream, lambda: sc.expand_dev(table, d_src, S + 2 * E, d_off, d_keys, d_proxy, total,
+                                                          d_total, stream=stream.cuda_stream), args.steps, 2)
+    assert int(d_total.cpu().numpy()[0]) == total
+    assert np.array_equal(d_keys.cpu().numpy().view(POLICY_KEY_DTYPE)[:total], want[1])
+    assert np.array_equal(d_proxy.cpu().numpy().view(np.uint16)[:total], want[2])
+    assert np.array_equal(d_off.cpu().numpy().view(np.uint64), want[0])
+    # ---- the parent's path on a sample of endpoints, extrapolated
+    parent = None
+    if args.cpu_seconds > 0:
+        sample = [int(sc.ids[e]) for e in eps[:2]]
+        t0 = time.perf_counter()
+        states = sc.endpoint_policy_map_states(sample)
+        parent_s = time.perf_counter() - t0
+        parent = {"kind": "extrapolated from a sample of endpoints (its own L4 rows: the repository's filters)",
+                  "sample_endpoints": len(sample), "sample_s": parent_s, "sample_entries": sum(map(len, states)),
+                  "all_endpoints_s_extrapolated": parent_s * E / len(sample)}
+    fused_s = sorted(fused)[1]
+    out_bytes = total * 10 + (R + 1) * 8
+    return {"kernels": ["selcache_expand_count_kernel", "selcache_expand_scan_kernel", "selcache_expand_emit_kernel"],
+            "rows": R, "l4_rows_per_endpoint": L4_ROWS, "l4_selector_pool": S, "entries": total,
+            "kernels_ms": expand_s * 1e3, "entries_per_s": total / expand_s,
+            "output_bytes": out_bytes, "output_gbps": out_bytes / expand_s / 1e9,
+            "fused_call_wall_ms": fused_s * 1e3, "fused_call": "match + reach + expand + copy back, median of 3",
+            "host_walker_ms": walker_s * 1e3, "host_walker_threads": threads,
+            "kernels_over_host_walker": walker_s / expand_s, "fused_over_host_walker": walker_s / fused_s,
+            "parent_endpoint_policy_map_states": parent}
+
+
 def bench_selcache(torch, dev, stream, cl, args, threads):
     """The selector cache at regeneration scale: 65,536 identities of 8
     labels, a 10,000-rule label repository, 256 endpoints.  Both kernels are
     checked against the library's host walker of the same compiled tables
     (cg_diag_selcache_*_host on `threads` threads — that run is also the CPU
-    leg), then timed on the stream.  resolve.py (the Python restatement the
+    leg), then timed on the stream; bench_selcache_expand adds the expansion
+    into policy-map entries.  resolve.py (the Python restatement the
     tables are pinned to) is timed on a sample of cells and extrapolated."""
     from cilium_amd import synth
     N_IDS, N_RULES, E = 65536, 10000, 256
@@ -790,6 +876,7 @@ def bench_selcache(torch, dev, stream, cl, args, threads):
             repo.allows_egress_label_access(me, peer)
             k += 1
         py_reach = 2 * k / (time.perf_counter() - t0)
+    expand = bench_selcache_expand(torch, dev, stream, sc, repo, eps, want_m, args, threads)
     cells, rcells = S * N_IDS, 2 * E * N_IDS
     ident_bytes = N_IDS * 8 * 16 + (N_IDS + 1) * 4
     out = line("selector x identity cells/s (selcache_match_kernel: EndpointSelector.Matches over the identity cache)",
@@ -809,6 +896,7 @@ def bench_selcache(torch, dev, stream, cl, args, threads):
                           "output_frac_of_hbm_peak": (2 * E * W * 8 + E) / reach_s / 1e9 / HBM_PEAK_GBPS,
                           "host_walker_ms": cpu_reach_s * 1e3, "host_walker_threads": threads,
                           "gpu_over_host_walker": cpu_reach_s / reach_s},
+                "expand": expand,
                 "python_resolve": {"kind": "extrapolated from a sample (single thread)",
                                    "match_cells_per_s": py_match, "match_sample_cells": 100_000,
                                    "match_full_s_extrapolated": cells / py_match if py_match else None,
