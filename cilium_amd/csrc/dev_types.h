@@ -312,6 +312,20 @@ CG_HD inline uint32_t raw_name_hash(uint32_t nl, uint32_t lo0, uint32_t lo1, uin
 // FNV-1a, 32 bit, over lowercase bytes
 CG_HD inline uint32_t raw_fnv(uint32_t h, uint8_t c) { return (h ^ c) * 16777619u; }
 constexpr uint32_t kRawFnvInit = 2166136261u;
+// A batch of raw requests in device memory: request i's head (or header
+// list) is raw[off[i], off[i + 1]), with its policy, direction, port and
+// remote identity (off has n + 1 entries).
+struct RawReqs {
+  const uint8_t* raw;
+  const uint64_t* off;
+  const uint32_t* policy;
+  const uint8_t* ingress;
+  const uint16_t* port;
+  const uint32_t* remote;
+  size_t n;
+  // requests [a, a + m) (offsets stay relative to raw)
+  RawReqs at(size_t a, size_t m) const { return {raw, off + a, policy + a, ingress + a, port + a, remote + a, m}; }
+};
 // ---- the persistent verdict ring (cg_http_ring_*, ring.cc): Envoy-sized
 // calls of header lists decided by a resident kernel that polls request
 // slots — no launch, no copies, no stream synchronization per call.  A

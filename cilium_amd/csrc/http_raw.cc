@@ -1,13 +1,18 @@
 // http_raw.cc — host side of the raw HTTP/1 path (kernels_http_raw.hip):
-// the snapshot's device tables for it, and the launch sequence
-//   scan → (bucket counts to the host) → layout → rank → build → http_kernel
-// on one stream.  The host step is the layout of a few thousand bucket
-// counts (chunks, runs of equal-units tiles, bucket cursors); request bytes
-// never leave the device.  CILIUM_GPU_RAW_LAYOUT=device selects the
-// device-layout sequence instead (raw_device_layout):
+// the snapshot's device tables for it, and its two launch sequences over a
+// call's requests (RawReqs).  Both begin with a scan launch — one front end
+// (raw_scan_waves) under either scan kernel, plus the kernel for the
+// requests it deferred — and differ in who lays the batch out.  The default,
+// the device-layout sequence (raw_device_layout):
 //   clear → scan (+ deferred) → seal → http_kernel → walk
 // per sub-batch, all on the caller's stream, with no copy back and no host
 // synchronization (the layout is raw_seal_kernel's).
+// CILIUM_GPU_RAW_LAYOUT=host selects the host-layout sequence (raw_sequential):
+//   scan (+ deferred) → (bucket counts to the host) → layout → rank → build
+//   → http_kernel
+// on one stream.  The host step is the layout of a few thousand bucket
+// counts (chunks, runs of equal-units tiles, bucket cursors); request bytes
+// never leave the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -133,12 +138,7 @@ struct RawCall {
   StagingSlot* sl;
   int cus;
   RawInput in;
-  const uint8_t* d_raw;
-  const uint64_t* d_off;
-  size_t n;
-  const uint32_t *d_policy, *d_remote;
-  const uint8_t* d_ingress;
-  const uint16_t* d_port;
+  RawReqs q;
   uint8_t* d_out;
   hipStream_t st;
   // set by raw_scan_phase
@@ -151,12 +151,7 @@ struct RawCall {
   uint32_t *bbase = nullptr, nblk = 0;
   RawCall half(size_t a, size_t m) const {
     RawCall c = *this;
-    c.d_off = d_off + a;
-    c.n = m;
-    c.d_policy = d_policy + a;
-    c.d_ingress = d_ingress + a;
-    c.d_port = d_port + a;
-    c.d_remote = d_remote + a;
+    c.q = q.at(a, m);
     c.d_out = d_out + a;
     return c;
   }
@@ -178,8 +173,8 @@ bool raw_scan_phase(RawCall& c) {
   c.ovf = (unsigned long long*)(small + hist_bytes);
   hip_check(hipMemsetAsync(small, 0, hist_bytes + 16, c.st), "hipMemsetAsync");
   // the head bytes [off[0], off[n]) size the string buffer
-  hip_check(hipMemcpyAsync(small + hist_bytes + 16, c.d_off + c.n, 8, hipMemcpyDeviceToDevice, c.st), "D2D");
-  hip_check(hipMemcpyAsync(small + hist_bytes + 8, c.d_off, 8, hipMemcpyDeviceToDevice, c.st), "D2D");
+  hip_check(hipMemcpyAsync(small + hist_bytes + 16, c.q.off + c.q.n, 8, hipMemcpyDeviceToDevice, c.st), "D2D");
+  hip_check(hipMemcpyAsync(small + hist_bytes + 8, c.q.off, 8, hipMemcpyDeviceToDevice, c.st), "D2D");
   c.hh = (uint8_t*)c.sl->host_buf(8, hist_bytes + 24);
   hip_check(hipMemcpyAsync(c.hh, small, hist_bytes + 24, hipMemcpyDeviceToHost, c.st), "D2H");
   hip_check(hipStreamSynchronize(c.st), "hipStreamSynchronize");
@@ -197,23 +192,22 @@ bool raw_scan_phase(RawCall& c) {
   // (+128: room to move a record to a line start, kernels_http_raw.hip rec_off)
   const uint32_t cst = (uint32_t)((2 * std::max<size_t>(s.raw.nfields, 1) + 48 + 15) & ~(size_t)15) + 128;
   // (+256: the build kernel reads whole 16-B chunks up to 8 units past a record's start)
-  const size_t sbytes = ((o1 - o0 + 15) & ~(uint64_t)15) + (size_t)cst * c.n + 256;
+  const size_t sbytes = ((o1 - o0 + 15) & ~(uint64_t)15) + (size_t)cst * c.q.n + 256;
   if (sbytes / 16 >= (1ull << 32)) {
-    if (c.n < 2) fail(CG_INVALID_ARGUMENT, "raw head too large");
+    if (c.q.n < 2) fail(CG_INVALID_ARGUMENT, "raw head too large");
     return false;
   }
   c.sbuf = (uint8_t*)c.sl->dev_buf(15, sbytes);
-  c.rinfo = c.sl->dev_buf(9, c.n * 8);
+  c.rinfo = c.sl->dev_buf(9, c.q.n * 8);
   // per-block bucket counts → per-block slot offsets (when the bucket
   // counters fit the kernels' LDS), else one global histogram
   const bool lds_keys = http_raw_lds_keys(s.raw);
   const bool lists = c.in == RawInput::Lists;
-  c.nblk = (uint32_t)http_raw_grid(s.raw, lists, c.n, c.cus);
+  c.nblk = (uint32_t)http_raw_grid(s.raw, lists, c.q.n, c.cus);
   uint32_t* bcount = lds_keys ? (uint32_t*)c.sl->dev_buf(16, (size_t)G * K * c.nblk * 4) : c.hist;
   c.bbase = lds_keys ? (uint32_t*)c.sl->dev_buf(17, (size_t)G * K * c.nblk * 4) : nullptr;
-  auto* dlist = (uint32_t*)c.sl->dev_buf(18, c.n * 4);
-  hip_check(launch_http_raw_scan(s.raw, lists, c.d_raw, c.d_off, c.n, c.d_policy, c.d_ingress, c.d_port, bcount,
-                                 c.rinfo, c.d_remote, c.sbuf, cst, c.ovf, dlist, dcount, c.st, c.cus),
+  auto* dlist = (uint32_t*)c.sl->dev_buf(18, c.q.n * 4);
+  hip_check(launch_http_raw_scan(s.raw, lists, c.q, bcount, c.rinfo, c.sbuf, cst, c.ovf, dlist, dcount, c.st, c.cus),
             "raw scan kernel launch");
   if (lds_keys)
     hip_check(launch_http_raw_prefix(bcount, G * K, c.nblk, c.bbase, c.hist, c.st), "raw prefix kernel launch");
@@ -239,7 +233,7 @@ bool raw_rest_phase(RawCall& c) {
   // strings need more than 256 MiB of arena runs as two halves (one head is
   // at most kRawMaxHead bytes, so halving always ends)
   if (ovf_bytes / 16 >= (1ull << 24)) {
-    if (c.n < 2) fail(CG_INVALID_ARGUMENT, "overflow arena beyond 256 MiB");
+    if (c.q.n < 2) fail(CG_INVALID_ARGUMENT, "overflow arena beyond 256 MiB");
     return false;
   }
   // ---- layout: groups in program order (then allow, deny), 64-slot tiles,
@@ -313,7 +307,7 @@ bool raw_rest_phase(RawCall& c) {
   auto* ttab = (HttpTile*)(batch + hdr.ttab_off);
   uint8_t* tdata = batch + hdr.tiles_off;
   const bool lists = c.in == RawInput::Lists;
-  hip_check(launch_http_raw_rank(s.raw, lists, c.n, c.rinfo, d_cursor, c.bbase, order, c.st, c.cus),
+  hip_check(launch_http_raw_rank(s.raw, lists, c.q.n, c.rinfo, d_cursor, c.bbase, order, c.st, c.cus),
             "raw rank kernel launch");
   hip_check(launch_http_raw_build(s.raw, d_runs, (uint32_t)runs.size(), tiles, ttab, tdata, order, c.sbuf, arena,
                                   c.ovf + 1, c.st, c.cus),
@@ -325,11 +319,11 @@ bool raw_rest_phase(RawCall& c) {
 // A call (or half) run start to end on its stream; halves when it is too
 // large for one pass.
 void raw_sequential(RawCall c) {
-  if (!c.n) return;
+  if (!c.q.n) return;
   if (!raw_scan_phase(c) || !raw_rest_phase(c)) {
-    const size_t h = c.n / 2;
+    const size_t h = c.q.n / 2;
     raw_sequential(c.half(0, h));
-    raw_sequential(c.half(h, c.n - h));
+    raw_sequential(c.half(h, c.q.n - h));
     return;
   }
   // the workspace belongs to the lease: done before it is handed back
@@ -353,9 +347,9 @@ uint32_t floor_pow2(uint32_t x) {
 // One sub-batch of the device-layout path, enqueued on `st`: clear the
 // counters and tile table, scan, seal, http_kernel, walk.  The workspace is
 // the slot's buffers 19..26 (the default sequence's are 8..18).
-void raw_dl_subbatch(const HttpSnapshot& s, StagingSlot& sl, int cus, bool lists, const uint8_t* d_raw,
-                  const uint64_t* d_off, size_t m, const uint32_t* d_policy, const uint8_t* d_ingress,
-                  const uint16_t* d_port, const uint32_t* d_remote, uint8_t* d_out, hipStream_t st) {
+void raw_dl_subbatch(const HttpSnapshot& s, StagingSlot& sl, int cus, bool lists, const RawReqs& q, uint8_t* d_out,
+                     hipStream_t st) {
+  const size_t m = q.n;
   // slot counters striped per workgroup (RawLayoutDev.stripes): a bucket
   // key's requests take slots from `stripes` counters, so the returning
   // atomics of a hot key do not serialize on one address (8: measured best
@@ -423,22 +417,18 @@ void raw_dl_subbatch(const HttpSnapshot& s, StagingSlot& sl, int cus, bool lists
   L.stripes = S;
   hip_check(hipMemsetAsync(ctl, 0, ctl_bytes, st), "hipMemsetAsync");
   hip_check(hipMemsetAsync(L.ttab, 0, sizeof(HttpTile) * maxtiles, st), "hipMemsetAsync");
-  hip_check(launch_http_raw_dl_scan(s.raw, lists, d_raw, d_off, m, d_policy, d_ingress, d_port, d_remote, L, st, cus),
-            "raw scan kernel launch");
+  hip_check(launch_http_raw_dl_scan(s.raw, lists, q, L, st, cus), "raw scan kernel launch");
   hip_check(launch_http_raw_seal(s.raw, L, batch, s.epoch, ttab_off, tiles_off, total, st), "raw seal kernel launch");
   // the scan wrote raw bytes: class-mode programs code them as they walk
   hip_check(launch_http(s.dev, batch, maxtiles * 64, nullptr, d_out, st, cus, L.order, nullptr, (uint32_t)m, s.raw.codes),
             "http kernel launch");
-  hip_check(launch_http_raw_walk(s.dev, s.raw, lists, d_raw, d_off, d_policy, d_ingress, d_port, d_remote, L, d_out,
-                                 st, cus),
-            "raw walk kernel launch");
+  hip_check(launch_http_raw_walk(s.dev, s.raw, lists, q, L, d_out, st, cus), "raw walk kernel launch");
 }
 
 // The device-layout path: sub-batches enqueued on `stream`, nothing waited
 // for on the host.
-void raw_device_layout(const HttpSnapshot& s, StagingSlot& sl, int cus, bool lists, const uint8_t* d_raw,
-                       const uint64_t* d_off, size_t n, const uint32_t* d_policy, const uint8_t* d_ingress,
-                       const uint16_t* d_port, const uint32_t* d_remote, uint8_t* d_out, void* stream) {
+void raw_device_layout(const HttpSnapshot& s, StagingSlot& sl, int cus, bool lists, const RawReqs& q, uint8_t* d_out,
+                       void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   // the slot's last raw call may still be queued on another stream: this
   // stream waits for it on the device (no host wait)
@@ -447,11 +437,7 @@ void raw_device_layout(const HttpSnapshot& s, StagingSlot& sl, int cus, bool lis
   // to 2^27 for the measurements of larger ones)
   size_t sub = kRawSubBatch;
   if (const char* v = getenv("CILIUM_GPU_RAW_SUBBATCH")) sub = std::min(kRawSubBatchMax, std::max<size_t>(64, strtoull(v, nullptr, 10)));
-  for (size_t a = 0; a < n; a += sub) {
-    const size_t m = std::min(sub, n - a);
-    raw_dl_subbatch(s, sl, cus, lists, d_raw, d_off + a, m, d_policy + a, d_ingress + a, d_port + a, d_remote + a,
-                 d_out + a, st);
-  }
+  for (size_t a = 0; a < q.n; a += sub) raw_dl_subbatch(s, sl, cus, lists, q.at(a, std::min(sub, q.n - a)), d_out + a, st);
   if (!sl.raw_ev) {
     hipEvent_t e;
     hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
@@ -481,12 +467,12 @@ void http_verdicts_raw_on(const HttpSnapshot& s, StagingSlot& sl, int cus, RawIn
                                : "raw HTTP/1 heads: the snapshot has more than " + std::to_string(kRawMaxFields) +
                                      " header fields, or is a proxylib snapshot");
   if (!n) return;
+  const RawReqs q{d_raw, d_off, d_policy, d_ingress, d_port, d_remote, n};
   if (device_layout_selected()) {
-    raw_device_layout(s, sl, cus, lists, d_raw, d_off, n, d_policy, d_ingress, d_port, d_remote, d_out, stream);
+    raw_device_layout(s, sl, cus, lists, q, d_out, stream);
     return;
   }
-  raw_sequential(RawCall{&s, &sl, cus, in, d_raw, d_off, n, d_policy, d_remote, d_ingress, d_port, d_out,
-                         (hipStream_t)stream});
+  raw_sequential(RawCall{&s, &sl, cus, in, q, d_out, (hipStream_t)stream});
 }
 
 }  // namespace cg

@@ -43,25 +43,29 @@ int launch_kafka_decode(const KafkaDictDev& topics, const KafkaDictDev& clients,
                         uint32_t* arena, size_t arena_cap, unsigned long long* ctr, uint8_t* status, void* stream,
                         int cus, uint32_t* defer_list, uint8_t* zarena, size_t zcap);
 
-// Raw HTTP/1 heads → batch (kernels_http_raw.hip; sequence in http_raw.cc).
-// The scan and rank kernels run http_raw_grid(R, lists, n, cus) blocks over the
-// requests in the same order.  With http_raw_lds_keys(R) the scan writes
+// Raw HTTP/1 heads → batch (kernels_http_raw.hip; sequences in http_raw.cc).
+// Both sequences take the requests as a RawReqs (dev_types.h) and start with
+// a scan launch — the scan kernel, whose front end (raw_scan_waves) parses
+// the requests that lie inside their wave's LDS stage, and a second kernel
+// that finishes the others from the scan's deferred list.  lists: the
+// requests are cg_http_pack header lists instead of HTTP/1 heads.
+//
+// The host-layout sequence (CILIUM_GPU_RAW_LAYOUT=host).  The scan and rank
+// kernels run http_raw_grid(R, lists, n, cus) blocks over the requests in
+// the same order.  With http_raw_lds_keys(R) the scan writes
 // per-block bucket counts (counts[key * grid + block]) and raw_prefix turns
 // them into per-block slot offsets (bbase) and totals (hist); otherwise the
 // scan adds into a global histogram (counts = hist) and the rank takes slots
 // from global cursors.  sbuf: the request-ordered string buffer
-// (records per request, http_raw.cc), cst its per-request stride.  lists:
-// the requests are cg_http_pack header lists instead of HTTP/1 heads (a list
-// longer than kFieldsMaxList sets kRawListTooLong in *ovf_bytes).  Requests
-// outside their wave's LDS stage are appended to dlist (*dcount, zeroed by
-// the caller; room for n) and finished by a second kernel of the launch.
+// (records per request, http_raw.cc), cst its per-request stride.  A list
+// longer than kFieldsMaxList sets kRawListTooLong in *ovf_bytes.  The
+// deferred list is dlist (*dcount, zeroed by the caller; room for n).
 constexpr unsigned long long kRawListTooLong = 1ull << 63;
 size_t http_raw_grid(const HttpRawDev& R, bool lists, size_t n, int cus);
 bool http_raw_lds_keys(const HttpRawDev& R);
-int launch_http_raw_scan(const HttpRawDev& R, bool lists, const uint8_t* raw, const uint64_t* off, size_t n,
-                         const uint32_t* policy, const uint8_t* ingress, const uint16_t* port, uint32_t* counts,
-                         void* rinfo, const uint32_t* remote, uint8_t* sbuf, uint32_t cst,
-                         unsigned long long* ovf_bytes, uint32_t* dlist, uint32_t* dcount, void* stream, int cus);
+int launch_http_raw_scan(const HttpRawDev& R, bool lists, const RawReqs& q, uint32_t* counts, void* rinfo,
+                         uint8_t* sbuf, uint32_t cst, unsigned long long* ovf_bytes, uint32_t* dlist,
+                         uint32_t* dcount, void* stream, int cus);
 int launch_http_raw_prefix(const uint32_t* bcount, uint32_t nkeys, uint32_t nblk, uint32_t* bbase, uint32_t* hist,
                            void* stream);
 int launch_http_raw_rank(const HttpRawDev& R, bool lists, size_t n, const void* rinfo, uint32_t* cursor,
@@ -70,24 +74,19 @@ int launch_http_raw_build(const HttpRawDev& R, const HttpRawRun* runs, uint32_t 
                           HttpTile* ttab, uint8_t* tiles, uint32_t* order, const uint8_t* sbuf, uint8_t* arena,
                           unsigned long long* arena_cursor, void* stream, int cus);
 
-// The device-layout path (CILIUM_GPU_RAW_LAYOUT=device; sequence, all on
-// one stream with no host round trip, in http_raw.cc):
-// launch_http_raw_dl_scan (scan + deferred requests) puts each request into its
-// slot of the batch laid out by L (dev_types.h RawLayoutDev) or on L's walk
-// list; launch_http_raw_seal pads the last tiles and writes the chunk table
-// and header; then launch_http over the batch (order = L.order) and
-// launch_http_raw_walk for the walk list.  lists: the requests are
-// cg_http_pack header lists instead of HTTP/1 heads.
+// The device-layout sequence (the default; all on one stream with no host
+// round trip): launch_http_raw_dl_scan puts each request into its slot of
+// the batch laid out by L (dev_types.h RawLayoutDev) or on L's walk list;
+// launch_http_raw_seal pads the last tiles and writes the chunk table and
+// header; then launch_http over the batch (order = L.order) and
+// launch_http_raw_walk for the walk list.
 size_t http_raw_dl_grid(const HttpRawDev& R, bool lists, size_t n, int cus);
-bool http_raw_seal_sorts(const HttpRawDev& R);
-int launch_http_raw_dl_scan(const HttpRawDev& R, bool lists, const uint8_t* raw, const uint64_t* off, size_t n,
-                            const uint32_t* policy, const uint8_t* ingress, const uint16_t* port,
-                            const uint32_t* remote, const RawLayoutDev& L, void* stream, int cus);
+int launch_http_raw_dl_scan(const HttpRawDev& R, bool lists, const RawReqs& q, const RawLayoutDev& L, void* stream,
+                            int cus);
 int launch_http_raw_seal(const HttpRawDev& R, const RawLayoutDev& L, void* batch, uint32_t epoch, uint64_t ttab_off,
                          uint64_t tiles_off, uint64_t total_bytes, void* stream);
-int launch_http_raw_walk(const HttpDev& T, const HttpRawDev& R, bool lists, const uint8_t* raw, const uint64_t* off,
-                         const uint32_t* policy, const uint8_t* ingress, const uint16_t* port, const uint32_t* remote,
-                         const RawLayoutDev& L, uint8_t* out, void* stream, int cus);
+int launch_http_raw_walk(const HttpDev& T, const HttpRawDev& R, bool lists, const RawReqs& q, const RawLayoutDev& L,
+                         uint8_t* out, void* stream, int cus);
 
 // The persistent verdict ring (ring.cc): nwg one-wave workgroups serving
 // the slots of G until its stop word, idle_ticks without a call or

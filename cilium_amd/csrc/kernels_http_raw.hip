@@ -5,12 +5,19 @@
 // The steps of http_parse.cc (the codec: request line, header fields, Host →
 // :authority, rejected heads) and http_pack.cc (program lookup, the walked
 // string v_1 SEP .. v_F SEP / REST, class codes, grouping by program and
-// string units):
-//   raw_scan_kernel   one lane per head (the wave's heads staged in LDS):
-//                     parse, program, the walked string class-coded into a
-//                     request-ordered string buffer (16-byte aligned per
-//                     request), bucket key (program group × string units)
-//                     and the per-block bucket counts
+// string units).  Both launch sequences of http_raw.cc start with the same
+// scan front end:
+//   raw_scan_waves    one lane per head, a wave's 64 heads staged in LDS
+//                     through a three-deep software pipeline: program
+//                     lookup, structural masks, the parse into value spans;
+//                     heads outside their wave's stage go on a deferred list
+//                     for a one-lane-per-request kernel that reads HBM
+// and differ in what a scan kernel (its sink) does with a parsed request.
+// The host-layout sequence (CILIUM_GPU_RAW_LAYOUT=host):
+//   raw_scan_kernel   the walked string into a request-ordered string buffer
+//                     (16-byte aligned per request), bucket key (program
+//                     group × string units) and the per-block bucket counts
+//   raw_defer_kernel  the same for the deferred requests
 //   (host)            bucket counts → chunks, runs of equal-units tiles,
 //                     bucket cursors
 //   raw_rank_kernel   a slot per request from its bucket cursor: order[slot]
@@ -22,7 +29,9 @@
 //   http_kernel       the verdicts, written straight to request order
 //                     through order[] (kernels_http.hip VOut)
 // Slots within a bucket come in atomic order: the verdicts are per request,
-// so they do not depend on it.
+// so they do not depend on it.  The device-layout sequence (the default)
+// needs no host step: raw_scan_dl_kernel's sink puts each request straight
+// into its slot of the batch (see "the device-layout path" below).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -49,12 +58,40 @@ constexpr uint32_t kRawWaves = kRawThreads / 64;
 
 // CG_RAW_CLOCKS (experiment builds only, tools/exp_http.py raw_clocks): the
 // scan's phases timed per wave with the shader clock; one wave prints its
-// totals at the end
+// totals at the end.  The front end (raw_scan_waves) marks the start of an
+// iteration and the ends of its stage store, masks and parse; a scan
+// kernel's sink marks once in its middle (host layout: string emitted;
+// device layout: slot taken).  Without the flag RawClocks is empty.
 #ifdef CG_RAW_CLOCKS
-#define RAW_CLK(v) v = clock64()
-#define RAW_ACC(slot, a, b) clk[slot] += (b) - (a)
-// inside parse_head_fast: time since the last mark into g_pclk[slot]
 __device__ unsigned long long g_pclk[8];
+struct RawClocks {
+  enum { kStart, kStaged, kMasks, kParsed, kSinkMid, kMarks };
+  uint64_t at[kMarks] = {}, sum[kMarks] = {}, total = 0, iters = 0;
+  __device__ __forceinline__ void mark(int k) { at[k] = clock64(); }
+  // an iteration's end: each phase is the time from the previous mark (a
+  // mark not reached this iteration takes none)
+  __device__ __forceinline__ void end() {
+    const uint64_t now = clock64();
+    for (int k = 1; k < kMarks; ++k) {
+      at[k] = max(at[k], at[k - 1]);
+      sum[k - 1] += at[k] - at[k - 1];
+    }
+    sum[kMarks - 1] += now - at[kMarks - 1];
+    total += now - at[0];
+    ++iters;
+  }
+  // who: the kernel and its sink's phases before and after kSinkMid
+  __device__ __forceinline__ void print(const char* who) const {
+    if (blockIdx.x != 7 || threadIdx.x != 64) return;
+    printf("%s clocks (wave 1 of block 7, %llu iterations): stage %llu masks %llu parse %llu sink before %llu after %llu "
+           "total %llu\n",
+           who, (unsigned long long)iters, (unsigned long long)sum[0], (unsigned long long)sum[1], (unsigned long long)sum[2],
+           (unsigned long long)sum[3], (unsigned long long)sum[4], (unsigned long long)total);
+    printf("parse clocks: request line %llu, line reads %llu, values %llu, names %llu, end %llu\n", g_pclk[0], g_pclk[1],
+           g_pclk[2], g_pclk[3], g_pclk[4]);
+  }
+};
+// inside parse_head_fast: time since the last mark into g_pclk[slot]
 #define RAW_PMARK(slot)                                                           \
   do {                                                                           \
     const uint64_t now_ = clock64();                                             \
@@ -63,8 +100,12 @@ __device__ unsigned long long g_pclk[8];
   } while (0)
 #define RAW_PSTART uint64_t pm_ = clock64()
 #else
-#define RAW_CLK(v)
-#define RAW_ACC(slot, a, b)
+struct RawClocks {
+  enum { kStart, kStaged, kMasks, kParsed, kSinkMid };
+  __device__ __forceinline__ void mark(int) {}
+  __device__ __forceinline__ void end() {}
+  __device__ __forceinline__ void print(const char*) const {}
+};
 #define RAW_PMARK(slot)
 #define RAW_PSTART
 #endif
@@ -1053,10 +1094,11 @@ __device__ __forceinline__ void stage_tables(const HttpRawDev& R, lds_u32* t, Ld
   for (uint32_t k = threadIdx.x; k < w.df; k += blockDim.x) tdf[k] = R.dflt[k];
   T = LdsTabs{t, tfs, tpk, tpv, twb, tdf, (const lds_u8*)tfn};
 }
-__device__ __forceinline__ void stage_tables(const HttpRawDev& R, lds_u32*, GlbTabs& T) {
-  T = GlbTabs{(glb_u32*)R.nkeys, (glb_u32*)R.fslots, (glb_u32*)R.phash_keys, (glb_u32*)R.phash_vals,
-              (glb_u32*)R.walk_bits, (glb_u32*)R.dflt, (glb_u8*)R.fnames};
+__device__ __forceinline__ GlbTabs glb_tabs(const HttpRawDev& R) {
+  return GlbTabs{(glb_u32*)R.nkeys, (glb_u32*)R.fslots, (glb_u32*)R.phash_keys, (glb_u32*)R.phash_vals,
+                 (glb_u32*)R.walk_bits, (glb_u32*)R.dflt, (glb_u8*)R.fnames};
 }
+__device__ __forceinline__ void stage_tables(const HttpRawDev& R, lds_u32*, GlbTabs& T) { T = glb_tabs(R); }
 // 16-byte chunks of a lane's output string: stored to dst, then dst +=
 // stride (uint4 units: a tile's next string unit, or the next arena line).
 struct Out16 {
@@ -1169,11 +1211,7 @@ __device__ __forceinline__ uint64_t rec_off(uint64_t head_rel, size_t i, uint32_
   return ((head_rel + 15) & ~15ull) + (uint64_t)cst * i;
 }
 
-// ---- pass 1: parse, program, string length, bucket key, the request's
-// record in the string buffer; per-block bucket counts (bcount[key * gridDim.x + block],
-// lds_keys) or a global histogram.  kLists: header lists, not heads.
-// Requests inside the wave's stage parse over its structural bitmaps;
-// the others are deferred to raw_defer_kernel.
+// ---- the scan front end (raw_scan_waves) and what it is made of ----------
 // A lane's request inputs, loaded two iterations ahead of their use.
 struct RawIn {
   uint32_t pol, rem, ip;  // policy, remote identity, ingress | port << 8
@@ -1182,19 +1220,17 @@ struct RawIn {
   __device__ __forceinline__ uint32_t ing() const { return ip & 0xFFu; }
   __device__ __forceinline__ uint32_t port() const { return ip >> 8; }
 };
-__device__ __forceinline__ RawIn raw_in(const uint64_t* __restrict__ off, const uint32_t* __restrict__ policy,
-                                        const uint8_t* __restrict__ ingress, const uint16_t* __restrict__ port,
-                                        const uint32_t* __restrict__ remote, size_t i, size_t n) {
+__device__ __forceinline__ RawIn raw_in(const RawReqs& Q, size_t i) {
   // unconditional loads, selects after them: a load skipped on some path
   // makes the compiler's wait for any older load a wait for every load
   // (vmcnt(0)), the next stage's included
-  const size_t j = i < n ? i : (n ? n - 1 : 0);
+  const size_t n = Q.n, j = i < n ? i : (n ? n - 1 : 0);
   RawIn r;
-  const uint32_t pol = policy[j];
+  const uint32_t pol = Q.policy[j];
   r.pol = i < n ? pol : 0xFFFFFFFFu;
-  r.ip = (uint32_t)ingress[j] | (uint32_t)port[j] << 8;
-  r.rem = remote[j];
-  const uint64_t a = off[j], b = off[j + 1];
+  r.ip = (uint32_t)Q.ingress[j] | (uint32_t)Q.port[j] << 8;
+  r.rem = Q.remote[j];
+  const uint64_t a = Q.off[j], b = Q.off[j + 1];
   r.a = i < n ? a : b;  // past n: empty at off[n]
   r.len = i < n && b > a ? (uint32_t)min<uint64_t>(b - a, 0xFFFFFFFFull) : 0u;
   return r;
@@ -1235,11 +1271,131 @@ __device__ __forceinline__ void stage_store(const StageRegs& S, lds_u8* stage, u
   for (uint32_t j = 0; j < kStageVecs; ++j) *(lds_v4*)(stage + (j * 64 + lane) * 16) = to_v4(S.v[j]);
 }
 
+// Append the lanes with `take` to a request list (count at *cnt): one atomic
+// per wave.
+__device__ __forceinline__ void list_append(uint32_t* list, uint32_t* cnt, bool take, uint32_t i, uint32_t lane) {
+  const unsigned long long m = __ballot(take);
+  if (!m) return;
+  const int first = __builtin_ctzll(m);
+  uint32_t base = 0;
+  if ((int)lane == first) base = atomicAdd(cnt, (uint32_t)__popcll(m));
+  base = (uint32_t)__shfl((int)base, first, 64);
+  if (take) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1))] = i;
+}
+
+// One lane's request as the front end hands it to a scan kernel's sink.
+struct ScanLane {
+  size_t i;            // the request
+  bool live, defer;    // i < n; outside the wave's stage: on the deferred list, not parsed
+  RawIn in;
+  uint32_t prog, hs;   // its program; its first byte's offset in the stage
+  bool ok;             // parsed and accepted (false for a request not parsed: dead, deferred, kProgDeny)
+  Parsed P;            // the fields it sets, their spans in sp[f * kRawThreads]
+  uint32_t len, last;  // accepted, under a walked program: the walked string's length, its last present field + 1 (else 0)
+  const lds_u8* stage;
+  lds_u32* sp;
+};
+
+// The front end of both scan kernels.  Dynamic LDS: [spans][wave stages]
+// [wave masks][tchar table][method table], then the caller's own (see
+// wave_stage); tables_at: where the lookup tables go when kLdsTabs.  One
+// lane per request, grid-stride over Q in rounds of a workgroup's 256: the
+// requests of a wave's round that lie outside its stage are appended to
+// dlist (*dcount) for the deferred kernel, the others are parsed (every
+// request but an unknown policy's: a head the codec rejects is denied in any
+// program), and the walked string of an accepted one is measured, inside the
+// same branch: a sink that branched on the parse's outcome again would hold a
+// second saved exec mask in scalar registers the scan does not have.
+// sink(ScanLane, clocks) runs once per lane and round of a
+// wave with a request, dead lanes included, in wave-uniform control flow.
+// kLists: header lists, not heads.  who: the kernel's name and its sink's two
+// phases, for the CG_RAW_CLOCKS line.
+template <bool kLists, bool kLdsTabs, class Sink>
+__device__ __forceinline__ void raw_scan_waves(const HttpRawDev& R, const RawReqs& Q, lds_u32* lds, lds_u32* tables_at,
+                                               uint32_t* dlist, uint32_t* dcount, const char* who, Sink sink) {
+  glb_u8* raw = (glb_u8*)Q.raw;
+  const size_t n = Q.n;
+  const uint32_t F = max(R.nfields, 1u), wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  lds_u32* sp = lds + threadIdx.x;  // this lane's spans: sp[f * kRawThreads]
+  lds_u8* stage = wave_stage(lds, F, wave);
+  lds_u32* masks = wave_masks(lds, F, wave);
+  lds_u8* tct = tchar_table(lds, F);
+  for (uint32_t b = threadIdx.x; b < 256; b += blockDim.x) tct[b] = kLists ? list_stop(b, R.raw_values) : !tchar(b);
+  const lds_u32* mtab = method_table(lds, F);
+  if (!kLists) stage_methods(method_table(lds, F));
+  // the lookup tables: LDS copies when they fit (kLdsTabs), else HBM
+  using Tabs = typename std::conditional<kLdsTabs, LdsTabs, GlbTabs>::type;
+  Tabs T;
+  stage_tables(R, tables_at, T);  // 16-byte aligned (field_of_words' key slots)
+  __syncthreads();
+  // software pipeline per wave: iteration k parses stage k from LDS while the
+  // stage of k + 1 is in flight into registers and the inputs of k + 2 load
+  const size_t gstride = (size_t)gridDim.x * kRawThreads;
+  size_t base = (size_t)blockIdx.x * kRawThreads;
+  // (a wave with no requests skips the loop)
+  RawIn cur = raw_in(Q, base + wave * 64 + lane);
+  RawIn nxt = raw_in(Q, base + gstride + wave * 64 + lane);
+  StageRegs S;
+  stage_load(raw, cur, lane, S, Q.off);
+  RawClocks ck;
+  for (; base < n; base += gstride) {
+    const size_t i0 = base + (size_t)wave * 64;
+    if (i0 >= n) break;  // wave-uniform
+    ck.mark(RawClocks::kStart);
+    const size_t i = i0 + lane;
+    const bool live = i < n;
+    const RawIn nn = raw_in(Q, base + 2 * gstride + wave * 64 + lane);
+    // the program (LDS tables): done while the stage's loads and the previous
+    // iteration's stores drain (the stage store below waits for both)
+    const uint32_t prog = live ? lookup_prog(R, T, cur.pol, cur.ing() != 0, cur.port()) : kProgDeny;
+    // stage k: registers → LDS (the previous iteration's reads are done)
+    wave_sync();
+    stage_store(S, stage, lane);
+    const uint64_t sbase = S.base;
+    const uint32_t slen = S.len;
+    // stage k + 1 into registers, under this iteration's parse
+    stage_load(raw, nxt, lane, S, Q.off);  // (past n: no bytes, nothing staged)
+    wave_sync();
+    ck.mark(RawClocks::kStaged);
+    if (kLists) build_masks_lists(stage, slen, tct, masks, lane);
+    else build_masks(stage, slen, tct, masks, lane);
+    wave_sync();
+    ck.mark(RawClocks::kMasks);
+    const uint32_t hn = cur.len;
+    const uint64_t ga = (uint64_t)(uintptr_t)(raw + cur.a);
+    const bool in = ga >= sbase && ga + hn <= sbase + slen;
+    const bool defer = live && prog != kProgDeny && !in;
+    list_append(dlist, dcount, defer, (uint32_t)i, lane);
+    ScanLane s{i, live, defer, cur, prog, (uint32_t)(ga - sbase), false, Parsed{0, 0}, 0, 0, stage, sp};
+    if (live && !defer && prog != kProgDeny) {
+      const uint32_t hs = s.hs;
+      s.ok = kLists ? (R.raw_values ? parse_list_fast(R, T, stage, masks, masks + kMaskWords, hs, hs + hn, sp, kRawThreads, s.P)
+                                    : parse_list_win(R, T, stage, masks, masks + kMaskWords, hs, hs + hn, sp, kRawThreads, s.P))
+                    : parse_head_fast(R, T, stage, masks, masks + kMaskWords, mtab, hs, hs + hn, sp, kRawThreads, s.P);
+      if (s.ok && walked_t(R, T, prog)) s.len = walked_len(R, s.P, &s.last);
+    }
+    ck.mark(RawClocks::kParsed);
+    sink(s, ck);
+    cur = nxt;
+    nxt = nn;
+    ck.end();
+  }
+  ck.print(who);
+}
+
 // Bucket key of a request: walked string units (0..8) or the overflow key.
 __device__ __forceinline__ uint32_t bucket_key(uint32_t len) {
   return len > CG_HTTP_SLOT_BYTES ? kRawKeys - 1 : (len + 15) / 16;
 }
 
+// ---- pass 1 of the host-layout sequence: the front end, then per request
+// the string length, bucket key and the request's record in the string
+// buffer; per-block bucket counts (bcount[key * gridDim.x + block], lds_keys:
+// LDS counters after the method table, the lookup tables after them) or a
+// global histogram.  (The kernels take the request arrays as separate
+// __restrict__ parameters and bundle them inside: with a RawReqs parameter
+// the registers are the same and the device-layout paths ran slower, DESIGN
+// §3.9.)
 template <bool kLists, bool kLdsTabs>
 __global__ __launch_bounds__(kRawThreads) void raw_scan_kernel(HttpRawDev R, const uint8_t* __restrict__ raw_g,
                                                                const uint64_t* __restrict__ off, size_t n,
@@ -1254,93 +1410,24 @@ __global__ __launch_bounds__(kRawThreads) void raw_scan_kernel(HttpRawDev R, con
                                                                uint32_t* __restrict__ dcount) {
   extern __shared__ uint32_t lds_[];
   lds_u32* lds = (lds_u32*)lds_;
-  glb_u8* raw = (glb_u8*)raw_g;
-  const uint32_t F = max(R.nfields, 1u), wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  lds_u32* sp = lds + threadIdx.x;  // this lane's spans: sp[f * kRawThreads]
-  lds_u8* stage = wave_stage(lds, F, wave);
-  lds_u32* masks = wave_masks(lds, F, wave);
-  lds_u8* tct = tchar_table(lds, F);
-  lds_u32* lk = key_counters(lds, F);
+  lds_u32* lk = key_counters(lds, max(R.nfields, 1u));
   const uint32_t nk = (R.nprogs + 2) * kRawKeys;
   if (lds_keys)
     for (uint32_t k = threadIdx.x; k < nk; k += blockDim.x) lk[k] = 0;
-  for (uint32_t b = threadIdx.x; b < 256; b += blockDim.x) tct[b] = kLists ? list_stop(b, R.raw_values) : !tchar(b);
-  const lds_u32* mtab = method_table(lds, F);
-  if (!kLists) stage_methods(method_table(lds, F));
-  // the lookup tables: LDS copies when they fit (kLdsTabs), else HBM
-  using Tabs = typename std::conditional<kLdsTabs, LdsTabs, GlbTabs>::type;
-  Tabs T;
-  stage_tables(R, lk + (lds_keys ? (nk + 3u) & ~3u : 0u), T);  // 16-byte aligned (field_of_words' key slots)
   const uint64_t off0 = off[0];
-  __syncthreads();
-  // software pipeline per wave: iteration k parses stage k from LDS while the
-  // stage of k + 1 is in flight into registers and the inputs of k + 2 load
-  const size_t gstride = (size_t)gridDim.x * kRawThreads;
-  size_t base = (size_t)blockIdx.x * kRawThreads;
-  // (a wave with no requests skips the loop and meets the others at the flush)
-  RawIn cur = raw_in(off, policy, ingress, port, remote, base + wave * 64 + lane, n);
-  RawIn nxt = raw_in(off, policy, ingress, port, remote, base + gstride + wave * 64 + lane, n);
-  StageRegs S;
-  stage_load(raw, cur, lane, S, off);
-#ifdef CG_RAW_CLOCKS
-  uint64_t clk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0;
-#endif
-  for (; base < n; base += gstride) {
-    const size_t i0 = base + (size_t)wave * 64;
-    if (i0 >= n) break;  // wave-uniform
-    RAW_CLK(c0);
-    const size_t i = i0 + lane;
-    const bool live = i < n;
-    const RawIn nn = raw_in(off, policy, ingress, port, remote, base + 2 * gstride + wave * 64 + lane, n);
-    // the program (LDS tables): done while the stage's loads and the previous
-    // iteration's record stores drain (the stage store below waits for both)
-    const uint32_t prog = live ? lookup_prog(R, T, cur.pol, cur.ing() != 0, cur.port()) : kProgDeny;
-    // stage k: registers → LDS (the previous iteration's reads are done)
-    wave_sync();
-    stage_store(S, stage, lane);
-    const uint64_t sbase = S.base;
-    const uint32_t slen = S.len;
-    // stage k + 1 into registers, under this iteration's parse
-    stage_load(raw, nxt, lane, S, off);  // (past n: no bytes, nothing staged)
-    wave_sync();
-    RAW_CLK(c1);
-    if (kLists) build_masks_lists(stage, slen, tct, masks, lane);
-    else build_masks(stage, slen, tct, masks, lane);
-    wave_sync();
-    RAW_CLK(c2);
-#ifdef CG_RAW_CLOCKS
-    c3 = c4 = c2;
-#endif
-    // every request but an unknown policy's is parsed: a head the codec
-    // rejects is denied in any program (flagged malformed)
-    const uint32_t hn = cur.len;
-    const uint64_t ga = (uint64_t)(uintptr_t)(raw + cur.a);
-    const bool in = ga >= sbase && ga + hn <= sbase + slen;
-    // a request outside the stage goes to raw_defer_kernel (one append per wave)
-    const bool defer = live && prog != kProgDeny && !in;
-    const unsigned long long dm = __ballot(defer);
-    if (dm) {
-      uint32_t dbase = 0;
-      if (lane == (uint32_t)__builtin_ctzll(dm)) dbase = atomicAdd(dcount, (uint32_t)__popcll(dm));
-      dbase = (uint32_t)__shfl((int)dbase, (int)__builtin_ctzll(dm), 64);
-      if (defer) dlist[dbase + (uint32_t)__popcll(dm & ((1ull << lane) - 1))] = (uint32_t)i;
-    }
-    if (live && !defer) {
-      uint32_t key = 0, len = 0, bad = 0;
-      uint64_t rpos = rec_off(cur.a - off0, i, cst);  // the record's byte offset (16-B aligned)
-      uint4* rec = reinterpret_cast<uint4*>(sbuf + rpos);
-      if (prog != kProgDeny) {
-        const uint32_t hs = (uint32_t)(ga - sbase);
-        Parsed P;
-        const bool ok = kLists ? (R.raw_values ? parse_list_fast(R, T, stage, masks, masks + kMaskWords, hs, hs + hn, sp, kRawThreads, P)
-                                             : parse_list_win(R, T, stage, masks, masks + kMaskWords, hs, hs + hn, sp, kRawThreads, P))
-                               : parse_head_fast(R, T, stage, masks, masks + kMaskWords, mtab, hs, hs + hn, sp, kRawThreads, P);
-        RAW_CLK(c3);
-        if (!ok) {
-          bad = 1;
-        } else if (walked_t(R, T, prog)) {
-          uint32_t last;
-          len = walked_len(R, P, &last);
+  const RawReqs Q{raw_g, off, policy, ingress, port, remote, n};
+  raw_scan_waves<kLists, kLdsTabs>(
+      R, Q, lds, lk + (lds_keys ? (nk + 3u) & ~3u : 0u), dlist, dcount,
+      "raw_scan (sink: emission | record header, rinfo, counters)",
+      [&](const ScanLane& s, RawClocks& ck) {
+        if (!s.live || s.defer) return;  // (a deferred request: raw_defer_kernel)
+        const size_t i = s.i;
+        const uint32_t prog = s.prog;
+        const uint32_t len = s.len, last = s.last;
+        uint32_t key = 0;
+        uint64_t rpos = rec_off(s.in.a - off0, i, cst);  // the record's byte offset (16-B aligned)
+        uint4* rec = reinterpret_cast<uint4*>(sbuf + rpos);
+        if (len) {  // (a walked string holds at least its REST byte or a separator)
           key = bucket_key(len);
           // a record the build reads (header + len rounded to 16) that would
           // straddle a 64-B sector (records up to 64 B) or a 128-B line
@@ -1351,52 +1438,56 @@ __global__ __launch_bounds__(kRawThreads) void raw_scan_kernel(HttpRawDev R, con
             rpos = (rpos + g - 1) & ~(uint64_t)(g - 1);
             rec = reinterpret_cast<uint4*>(sbuf + rpos);
           }
-          emit_direct(R, stage, hs, sp, kRawThreads, P, last, reinterpret_cast<uint8_t*>(rec + 1));
+          emit_direct(R, s.stage, s.hs, s.sp, kRawThreads, s.P, last, reinterpret_cast<uint8_t*>(rec + 1));
           if (len > CG_HTTP_SLOT_BYTES) atomicAdd(ovf_bytes, (unsigned long long)((4 + len + 15) & ~15u));
-          RAW_CLK(c4);
         }
-      }
-      const uint32_t flags = (cur.ing() ? CG_HTTP_F_INGRESS : 0u) | (bad ? CG_HTTP_F_MALFORMED : 0u) |
-                             (len > CG_HTTP_SLOT_BYTES ? CG_HTTP_F_OVERFLOW : 0u);
-      *rec = make_uint4((uint32_t)i, cur.rem, len | flags << 24, prog);
-      const uint32_t k = group_of(R, prog) * kRawKeys + key;
-      // for the rank: the bucket and the record (16-B units)
-      rinfo[i] = make_uint2(k, (uint32_t)(rpos / 16));
-      if (lds_keys) __hip_atomic_fetch_add(&lk[k], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      else atomicAdd(&counts[k], 1u);
-    }
-    cur = nxt;
-    nxt = nn;
-    RAW_CLK(c5);
-    RAW_ACC(0, c0, c1);  // stage store (waits for the stage's loads)
-    RAW_ACC(1, c1, c2);  // structural masks
-    RAW_ACC(2, c2, c3);  // program lookup + parse
-    RAW_ACC(3, c3, c4);  // string length + emission
-    RAW_ACC(4, c4, c5);  // record header, rinfo, counters
-    RAW_ACC(5, c0, c5);
-#ifdef CG_RAW_CLOCKS
-    clk[6] += 1;
-#endif
-  }
-#ifdef CG_RAW_CLOCKS
-  if (blockIdx.x == 7 && threadIdx.x == 64) {
-    printf("raw_scan clocks (wave 1 of block 7, %llu iterations): stage %llu masks %llu parse %llu emit %llu tail %llu total %llu\n",
-           (unsigned long long)clk[6], (unsigned long long)clk[0], (unsigned long long)clk[1], (unsigned long long)clk[2],
-           (unsigned long long)clk[3], (unsigned long long)clk[4], (unsigned long long)clk[5]);
-    printf("parse clocks: request line %llu, line reads %llu, values %llu, names %llu, end %llu\n", g_pclk[0], g_pclk[1],
-           g_pclk[2], g_pclk[3], g_pclk[4]);
-  }
-#endif
+        ck.mark(RawClocks::kSinkMid);  // emission before, record header, rinfo, counters after
+        const bool bad = prog != kProgDeny && !s.ok;  // parsed, rejected by the codec
+        const uint32_t flags = (s.in.ing() ? CG_HTTP_F_INGRESS : 0u) | (bad ? CG_HTTP_F_MALFORMED : 0u) |
+                               (len > CG_HTTP_SLOT_BYTES ? CG_HTTP_F_OVERFLOW : 0u);
+        *rec = make_uint4((uint32_t)i, s.in.rem, len | flags << 24, prog);
+        const uint32_t k = group_of(R, prog) * kRawKeys + key;
+        // for the rank: the bucket and the record (16-B units)
+        rinfo[i] = make_uint2(k, (uint32_t)(rpos / 16));
+        if (lds_keys) __hip_atomic_fetch_add(&lk[k], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        else atomicAdd(&counts[k], 1u);
+      });
+  // (a wave with no requests skipped the loop and meets the others here)
   if (lds_keys) {
     __syncthreads();
     for (uint32_t k = threadIdx.x; k < nk; k += blockDim.x) counts[(size_t)k * gridDim.x + blockIdx.x] = lk[k];
   }
 }
 
-// ---- pass 1b: the requests the scan deferred (heads / lists not inside
-// their wave's stage: long ones), one lane each, read byte by byte from HBM
-// through HeadReader with the tables in global memory.  Their bucket counts
-// go to the scan block that met them (nblk: the scan's grid), after it.
+// ---- the slow path: a request read from HBM by one lane through a
+// HeadReader, with the tables in global memory (the deferred and walk-list
+// kernels of both sequences).  Its length, program and reader:
+struct SlowReq {
+  uint64_t a;  // off[i]
+  uint32_t hn, prog;
+  HeadReader hr;
+};
+__device__ __forceinline__ SlowReq slow_req(const HttpRawDev& R, const GlbTabs& T, const uint8_t* raw,
+                                            const uint64_t* off, const uint32_t* policy, const uint8_t* ingress,
+                                            const uint16_t* port, size_t i) {
+  const uint64_t a = off[i], b = off[i + 1];
+  const uint32_t hn = b > a ? (uint32_t)min<uint64_t>(b - a, 0xFFFFFFFFull) : 0u;
+  return SlowReq{a, hn, lookup_prog(R, T, policy[i], ingress[i] != 0, port[i]),
+                 HeadReader((glb_u8*)raw + a, hn, (const lds_u8*)0, false)};
+}
+// Its spans into sp[f * kRawThreads] (kAbsentSpan for an absent field);
+// false: rejected by the codec, or a list whose spans would not fit 16-bit
+// offsets (hn > kFieldsMaxList, past Envoy's 60 KiB header limit).
+template <bool kLists>
+__device__ __forceinline__ bool slow_parse(const HttpRawDev& R, const GlbTabs& T, SlowReq& q, lds_u32* sp) {
+  return kLists ? q.hn <= kFieldsMaxList && parse_list_bytes(R, T, q.hr, sp, kRawThreads)
+                : parse_head(R, T, q.hr, sp, kRawThreads);
+}
+
+// ---- pass 1b of the host-layout sequence: the requests the scan deferred
+// (heads / lists not inside their wave's stage: long ones), one lane each.
+// Their bucket counts go to the scan block that met them (nblk: the scan's
+// grid), after it.
 template <bool kLists>
 __global__ __launch_bounds__(kRawThreads) void raw_defer_kernel(HttpRawDev R, const uint8_t* __restrict__ raw,
                                                                 const uint64_t* __restrict__ off,
@@ -1412,29 +1503,18 @@ __global__ __launch_bounds__(kRawThreads) void raw_defer_kernel(HttpRawDev R, co
                                                                 const uint32_t* __restrict__ dcount) {
   extern __shared__ uint32_t lds_[];
   lds_u32* sp = (lds_u32*)lds_ + threadIdx.x;
-  const GlbTabs T{(glb_u32*)R.nkeys, (glb_u32*)R.fslots, (glb_u32*)R.phash_keys, (glb_u32*)R.phash_vals,
-                  (glb_u32*)R.walk_bits, (glb_u32*)R.dflt, (glb_u8*)R.fnames};
+  const GlbTabs T = glb_tabs(R);
   const uint32_t nd = *dcount;
   const uint64_t off0 = off[0];
   for (uint32_t j = blockIdx.x * kRawThreads + threadIdx.x; j < nd; j += gridDim.x * kRawThreads) {
     const size_t i = dlist[j];
-    const uint64_t a = off[i], b = off[i + 1];
-    const uint32_t hn = b > a ? (uint32_t)min<uint64_t>(b - a, 0xFFFFFFFFull) : 0u;
-    const uint32_t prog = lookup_prog(R, T, policy[i], ingress[i] != 0, port[i]);
-    HeadReader hr((glb_u8*)raw + a, hn, (const lds_u8*)0, false);
+    SlowReq q = slow_req(R, T, raw, off, policy, ingress, port, i);
+    const uint64_t a = q.a;
+    const uint32_t prog = q.prog;
     uint32_t key = 0, len = 0, bad = 0;
     uint4* rec = reinterpret_cast<uint4*>(sbuf + rec_off(a - off0, i, cst));
-    bool ok;
-    if (kLists) {
-      if (hn > kFieldsMaxList) {  // spans would not fit: the call fails
-        atomicOr(ovf_bytes, kRawListTooLong);
-        ok = false;
-      } else {
-        ok = parse_list_bytes(R, T, hr, sp, kRawThreads);
-      }
-    } else {
-      ok = parse_head(R, T, hr, sp, kRawThreads);
-    }
+    if (kLists && q.hn > kFieldsMaxList) atomicOr(ovf_bytes, kRawListTooLong);  // spans would not fit: the call fails
+    const bool ok = slow_parse<kLists>(R, T, q, sp);
     if (!ok) {
       bad = 1;
     } else if (walked(R, prog)) {
@@ -1442,7 +1522,7 @@ __global__ __launch_bounds__(kRawThreads) void raw_defer_kernel(HttpRawDev R, co
       len = string_len(R, sp, kRawThreads, &last);
       key = bucket_key(len);
       Out16 o(rec + 1, 1);
-      emit_string(R, hr, sp, kRawThreads, last, o);
+      emit_string(R, q.hr, sp, kRawThreads, last, o);
       if (o.pos) o.flush();
       if (len > CG_HTTP_SLOT_BYTES) atomicAdd(ovf_bytes, (unsigned long long)((4 + len + 15) & ~15u));
     }
@@ -1665,7 +1745,8 @@ __global__ __launch_bounds__(kRawThreads) void raw_build_kernel(
 
 // ---- the device-layout path (CILIUM_GPU_RAW_LAYOUT=device, http_raw.cc) --
 // The steps of the path above without its host round trips:
-//   raw_scan_dl_kernel   parse as raw_scan_kernel, then the request takes a
+//   raw_scan_dl_kernel   the scan front end (raw_scan_waves), then its sink:
+//                        the request takes a
 //                        slot of its bucket (program group x string units)
 //                        from a per-bucket counter and writes its class-coded
 //                        string units, meta word and order entry straight
@@ -1799,24 +1880,11 @@ __device__ __forceinline__ void raw_fill(const RawLayoutDev& L, const RawSlot& s
   }
 }
 
-// Append the lanes with `take` to a request list (count at *cnt): one atomic
-// per wave.
-__device__ __forceinline__ void list_append(uint32_t* list, uint32_t* cnt, bool take, uint32_t i, uint32_t lane) {
-  const unsigned long long m = __ballot(take);
-  if (!m) return;
-  const int first = __builtin_ctzll(m);
-  uint32_t base = 0;
-  if ((int)lane == first) base = atomicAdd(cnt, (uint32_t)__popcll(m));
-  base = (uint32_t)__shfl((int)base, first, 64);
-  if (take) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1))] = i;
-}
-// ---- the scan: parse, program, string, slot and tile ---------------------
-// One lane per request, a wave's 64 heads (lists) staged in LDS: parse over
-// the structural bitmaps, look the program up, and put the request straight
-// into its slot of the device-built batch — class-coded string units, meta
-// word, order entry.  A request whose walked string passes the slot
-// (CG_HTTP_SLOT_BYTES) goes on the walk list; one outside its wave's stage on
-// the deferred list (raw_defer_kernel).  kLists: header lists, not heads.
+// ---- the scan: the front end, then string, slot and tile ------------------
+// A parsed request goes straight into its slot of the device-built batch —
+// string units (raw bytes), meta word, order entry.  A request whose walked
+// string passes the slot (CG_HTTP_SLOT_BYTES) goes on the walk list; one
+// outside its wave's stage on the deferred list (raw_defer_dl_kernel).
 template <bool kLists, bool kLdsTabs>
 __global__ __launch_bounds__(kRawThreads) void raw_scan_dl_kernel(HttpRawDev R, const uint8_t* __restrict__ raw_g,
                                                                const uint64_t* __restrict__ off, size_t n,
@@ -1826,111 +1894,30 @@ __global__ __launch_bounds__(kRawThreads) void raw_scan_dl_kernel(HttpRawDev R, 
                                                                const uint32_t* __restrict__ remote, RawLayoutDev L) {
   extern __shared__ uint32_t lds_[];
   lds_u32* lds = (lds_u32*)lds_;
-  glb_u8* raw = (glb_u8*)raw_g;
-  const uint32_t F = max(R.nfields, 1u), wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  lds_u32* sp = lds + threadIdx.x;  // this lane's spans: sp[f * kRawThreads]
-  lds_u8* stage = wave_stage(lds, F, wave);
-  lds_u32* masks = wave_masks(lds, F, wave);
-  lds_u8* tct = tchar_table(lds, F);
-  for (uint32_t b = threadIdx.x; b < 256; b += blockDim.x) tct[b] = kLists ? list_stop(b, R.raw_values) : !tchar(b);
-  const lds_u32* mtab = method_table(lds, F);
-  if (!kLists) stage_methods(method_table(lds, F));
-  // the lookup tables: LDS copies when they fit (kLdsTabs), else HBM
-  using Tabs = typename std::conditional<kLdsTabs, LdsTabs, GlbTabs>::type;
-  Tabs T;
-  stage_tables(R, raw_tables(lds, F), T);
-  __syncthreads();
-  // software pipeline per wave: iteration k parses stage k from LDS while the
-  // stage of k + 1 is in flight into registers and the inputs of k + 2 load
-  const size_t gstride = (size_t)gridDim.x * kRawThreads;
-  size_t base = (size_t)blockIdx.x * kRawThreads;
-  RawIn cur = raw_in(off, policy, ingress, port, remote, base + wave * 64 + lane, n);
-  RawIn nxt = raw_in(off, policy, ingress, port, remote, base + gstride + wave * 64 + lane, n);
-  StageRegs S;
-  stage_load(raw, cur, lane, S, off);
-  uint64_t clk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0;
-  for (; base < n; base += gstride) {
-    const size_t i0 = base + (size_t)wave * 64;
-    if (i0 >= n) break;  // wave-uniform
-    const size_t i = i0 + lane;
-    const bool live = i < n;
-    RAW_CLK(c0);
-    const RawIn nn = raw_in(off, policy, ingress, port, remote, base + 2 * gstride + wave * 64 + lane, n);
-    const uint32_t prog = live ? lookup_prog(R, T, cur.pol, cur.ing() != 0, cur.port()) : kProgDeny;
-    // stage k: registers → LDS (the previous iteration's reads are done)
-    wave_sync();
-    stage_store(S, stage, lane);
-    const uint64_t sbase = S.base;
-    const uint32_t slen = S.len;
-    // stage k + 1 into registers, under this iteration's parse
-    stage_load(raw, nxt, lane, S, off);  // (past n: no bytes, nothing staged)
-    wave_sync();
-    RAW_CLK(c1);
-    if (kLists) build_masks_lists(stage, slen, tct, masks, lane);
-    else build_masks(stage, slen, tct, masks, lane);
-    wave_sync();
-    RAW_CLK(c2);
-    // every request but an unknown policy's is parsed: a head the codec
-    // rejects is denied in any program (flagged malformed)
-    const uint32_t hn = cur.len;
-    const uint64_t ga = (uint64_t)(uintptr_t)(raw + cur.a);
-    const bool in = ga >= sbase && ga + hn <= sbase + slen;
-    const bool defer = live && prog != kProgDeny && !in;
-    list_append(L.dlist, &L.ctl[kRawCtlDefer], defer, (uint32_t)i, lane);
-    const uint32_t hs = (uint32_t)(ga - sbase);
-    uint32_t flags = cur.ing() ? CG_HTTP_F_INGRESS : 0u, units = 0, len = 0, last = 0;
-    bool walk = false;
-    Parsed P;
-    P.present = P.vsum = 0;
-    if (live && !defer && prog != kProgDeny) {
-      const bool ok = kLists ? (R.raw_values ? parse_list_fast(R, T, stage, masks, masks + kMaskWords, hs, hs + hn, sp, kRawThreads, P)
-                                             : parse_list_win(R, T, stage, masks, masks + kMaskWords, hs, hs + hn, sp, kRawThreads, P))
-                             : parse_head_fast(R, T, stage, masks, masks + kMaskWords, mtab, hs, hs + hn, sp, kRawThreads, P);
-      if (!ok) {
-        flags |= CG_HTTP_F_MALFORMED;
-      } else if (walked_t(R, T, prog)) {
-        len = walked_len(R, P, &last);
-        if (len > CG_HTTP_SLOT_BYTES) walk = true;
-        else units = (len + 15) / 16;
-      }
-    }
-    RAW_CLK(c3);
-    const bool want = live && !defer && !walk;
-    const RawSlot sl = raw_slot(L, want, raw_vkey(L, group_of(R, prog) * kRawUnits + units, blockIdx.x), prog);
-    RAW_CLK(c4);
-    walk |= want && !sl.ok;
-    list_append(L.walk, &L.ctl[kRawCtlWalk], walk, (uint32_t)i, lane);
-    if (want && sl.ok) {
-      raw_fill(L, sl, (uint32_t)i, cur.rem, flags, units, len, [&](uint4* dst) {
-        TileOut<false> o(dst, nullptr);  // raw bytes: http_kernel codes them
-        emit_stage(R, stage, hs, sp, kRawThreads, P, last, o);
+  const RawReqs Q{raw_g, off, policy, ingress, port, remote, n};
+  raw_scan_waves<kLists, kLdsTabs>(
+      R, Q, lds, raw_tables(lds, max(R.nfields, 1u)), L.dlist, &L.ctl[kRawCtlDefer],
+      "raw_scan_dl (sink: slot | lists, emission)",
+      [&](const ScanLane& s, RawClocks& ck) {
+        const uint32_t i = (uint32_t)s.i, prog = s.prog, lane = threadIdx.x & 63;
+        const bool mine = s.live && !s.defer;
+        const uint32_t len = s.len, last = s.last;
+        const uint32_t flags = (s.in.ing() ? CG_HTTP_F_INGRESS : 0u) |
+                               (mine && prog != kProgDeny && !s.ok ? CG_HTTP_F_MALFORMED : 0u);  // parsed, rejected
+        bool walk = len > CG_HTTP_SLOT_BYTES;
+        const uint32_t units = walk ? 0u : (len + 15) / 16;
+        const bool want = mine && !walk;
+        const RawSlot sl = raw_slot(L, want, raw_vkey(L, group_of(R, prog) * kRawUnits + units, blockIdx.x), prog);
+        ck.mark(RawClocks::kSinkMid);  // slot (atomic, directory) before, lists and emission after
+        walk |= want && !sl.ok;
+        list_append(L.walk, &L.ctl[kRawCtlWalk], walk, i, lane);
+        if (want && sl.ok) {
+          raw_fill(L, sl, i, s.in.rem, flags, units, len, [&](uint4* dst) {
+            TileOut<false> o(dst, nullptr);  // raw bytes: http_kernel codes them
+            emit_stage(R, s.stage, s.hs, s.sp, kRawThreads, s.P, last, o);
+          });
+        }
       });
-    }
-    RAW_CLK(c5);
-    RAW_ACC(0, c0, c1);  // program lookup, stage store (waits for the stage's loads)
-    RAW_ACC(1, c1, c2);  // structural masks
-    RAW_ACC(2, c2, c3);  // parse, walked length
-    RAW_ACC(3, c3, c4);  // slot (atomic, directory)
-    RAW_ACC(4, c4, c5);  // lists, emission
-    RAW_ACC(5, c0, c5);
-#ifdef CG_RAW_CLOCKS
-    clk[6] += 1;
-#endif
-    (void)c6;
-    cur = nxt;
-    nxt = nn;
-  }
-#ifdef CG_RAW_CLOCKS
-  if (blockIdx.x == 7 && threadIdx.x == 64) {
-    printf("raw_scan_dl clocks (wave 1 of block 7, %llu iterations): stage %llu masks %llu parse %llu slot %llu emit %llu total %llu\n",
-           (unsigned long long)clk[6], (unsigned long long)clk[0], (unsigned long long)clk[1], (unsigned long long)clk[2],
-           (unsigned long long)clk[3], (unsigned long long)clk[4], (unsigned long long)clk[5]);
-    printf("parse clocks: request line %llu, line reads %llu, values %llu, names %llu, end %llu\n", g_pclk[0], g_pclk[1],
-           g_pclk[2], g_pclk[3], g_pclk[4]);
-  }
-#else
-  (void)clk;
-#endif
 }
 
 // ---- the deferred requests (heads / lists not inside their wave's stage:
@@ -1945,26 +1932,19 @@ __global__ __launch_bounds__(kRawThreads) void raw_defer_dl_kernel(HttpRawDev R,
                                                                 const uint32_t* __restrict__ remote, RawLayoutDev L) {
   extern __shared__ uint32_t lds_[];
   lds_u32* sp = (lds_u32*)lds_ + threadIdx.x;
-  const GlbTabs T{(glb_u32*)R.nkeys, (glb_u32*)R.fslots, (glb_u32*)R.phash_keys, (glb_u32*)R.phash_vals,
-                  (glb_u32*)R.walk_bits, (glb_u32*)R.dflt, (glb_u8*)R.fnames};
+  const GlbTabs T = glb_tabs(R);
   const uint32_t nd = L.ctl[kRawCtlDefer], lane = threadIdx.x & 63;
   const uint32_t gs = gridDim.x * kRawThreads;
   for (uint32_t base = blockIdx.x * kRawThreads; base < nd; base += gs) {  // uniform per workgroup
     const uint32_t j = base + threadIdx.x;
     const bool live = j < nd;
-    const uint32_t i = live ? L.dlist[j] : 0u;
-    const uint64_t a = off[i], b = off[i + 1];
-    const uint32_t hn = b > a ? (uint32_t)min<uint64_t>(b - a, 0xFFFFFFFFull) : 0u;
-    const uint32_t prog = live ? lookup_prog(R, T, policy[i], ingress[i] != 0, port[i]) : kProgDeny;
-    HeadReader hr((glb_u8*)raw + a, hn, (const lds_u8*)0, false);
+    const uint32_t i = live ? L.dlist[j] : 0u;  // (a dead lane reads request 0 and keeps nothing of it)
+    SlowReq q = slow_req(R, T, raw, off, policy, ingress, port, i);
+    const uint32_t prog = live ? q.prog : kProgDeny;
     uint32_t flags = ingress[i] ? CG_HTTP_F_INGRESS : 0u, units = 0, len = 0, last = 0;
     bool walk = false;
     if (live) {
-      // a list's spans are 16-bit offsets: longer lists (past Envoy's 60 KiB
-      // header limit) are rejected
-      const bool ok = kLists ? hn <= kFieldsMaxList && parse_list_bytes(R, T, hr, sp, kRawThreads)
-                             : parse_head(R, T, hr, sp, kRawThreads);
-      if (!ok) {
+      if (!slow_parse<kLists>(R, T, q, sp)) {  // (a list past kFieldsMaxList: malformed)
         flags |= CG_HTTP_F_MALFORMED;
       } else if (walked(R, prog)) {
         len = string_len(R, sp, kRawThreads, &last);
@@ -1979,7 +1959,7 @@ __global__ __launch_bounds__(kRawThreads) void raw_defer_dl_kernel(HttpRawDev R,
     if (want && sl.ok) {
       raw_fill(L, sl, i, remote[i], flags, units, len, [&](uint4* dst) {
         TileOut<false> o(dst, nullptr);  // raw bytes: http_kernel codes them
-        emit_reader(R, hr, sp, kRawThreads, last, o);
+        emit_reader(R, q.hr, sp, kRawThreads, last, o);
       });
     }
   }
@@ -2161,19 +2141,14 @@ __global__ __launch_bounds__(kRawThreads) void raw_walk_kernel(HttpDev HT, HttpR
                                                                uint8_t* __restrict__ out) {
   extern __shared__ uint32_t lds_[];
   lds_u32* sp = (lds_u32*)lds_ + threadIdx.x;
-  const GlbTabs T{(glb_u32*)R.nkeys, (glb_u32*)R.fslots, (glb_u32*)R.phash_keys, (glb_u32*)R.phash_vals,
-                  (glb_u32*)R.walk_bits, (glb_u32*)R.dflt, (glb_u8*)R.fnames};
+  const GlbTabs T = glb_tabs(R);
   const uint32_t nw = L.ctl[kRawCtlWalk];
   for (uint32_t j = blockIdx.x * kRawThreads + threadIdx.x; j < nw; j += gridDim.x * kRawThreads) {
     const uint32_t i = L.walk[j];
-    const uint64_t a = off[i], b = off[i + 1];
-    const uint32_t hn = b > a ? (uint32_t)min<uint64_t>(b - a, 0xFFFFFFFFull) : 0u;
-    const uint32_t prog = lookup_prog(R, T, policy[i], ingress[i] != 0, port[i]);
-    HeadReader hr((glb_u8*)raw + a, hn, (const lds_u8*)0, false);
-    const bool ok = prog == kProgDeny ? false
-                    : kLists          ? hn <= kFieldsMaxList && parse_list_bytes(R, T, hr, sp, kRawThreads)
-                                      : parse_head(R, T, hr, sp, kRawThreads);
-    out[i] = (uint8_t)decide_request(HT, R, prog, ok, nullptr, nullptr, hr, sp, kRawThreads, remote[i]);
+    SlowReq q = slow_req(R, T, raw, off, policy, ingress, port, i);
+    // (an unknown policy's request is not parsed; a list past kFieldsMaxList is denied)
+    const bool ok = q.prog != kProgDeny && slow_parse<kLists>(R, T, q, sp);
+    out[i] = (uint8_t)decide_request(HT, R, q.prog, ok, nullptr, nullptr, q.hr, sp, kRawThreads, remote[i]);
   }
 }
 // ---- the persistent verdict ring (ring.cc; dev_types.h HttpRingDev) ------
@@ -2630,28 +2605,54 @@ unsigned grid_for(size_t n, int cus, unsigned per_cu) {
 
 // LDS of the scan / emit kernels (see wave_stage, key_counters)
 bool lds_tables_fit(const HttpRawDev& R) { return raw_tables_lds_words(R) * 4 <= 8 * 1024; }
-size_t raw_lds(const HttpRawDev& R, bool lds_keys, bool lds_codes) {
+size_t raw_lds(const HttpRawDev& R, bool lds_keys) {
   const size_t nk = ((size_t)R.nprogs + 2) * kRawKeys;
   return (size_t)std::max(R.nfields, 1u) * kRawThreads * 4 + kRawWaves * (size_t)kStage + kRawWaves * 2 * (kStage / 8) + kTctBytes +
          (lds_keys ? nk * 4 : 0) + (lds_tables_fit(R) ? (size_t)raw_tables_lds_words(R) * 4 : 0) +
-         (lds_codes ? (size_t)R.nprogs * 256 : 0) + 16 + 12;  // + slack: a quad read may pass the last stage by 7 bytes; the tables' alignment
+         16 + 12;  // + slack: a quad read may pass the last stage by 7 bytes; the tables' alignment
 }
-// code maps in LDS only while small: a larger table costs workgroups per CU
-// (occupancy) more than its global (L1-cached) lookups cost
-bool lds_codes_fit(const HttpRawDev& R) { return (size_t)R.nprogs * 256 <= 4 * 1024; }
 
+// The instances of the two scan kernels by [lists][tables in LDS], and the
+// one a call takes.
 using ScanKernel = decltype(&raw_scan_kernel<false, false>);
-ScanKernel scan_kernel_for(const HttpRawDev& R, bool lists) {
-  const bool tabs = lds_tables_fit(R);
-  if (lists) return tabs ? raw_scan_kernel<true, true> : raw_scan_kernel<true, false>;
-  return tabs ? raw_scan_kernel<false, true> : raw_scan_kernel<false, false>;
+using DlScanKernel = decltype(&raw_scan_dl_kernel<false, false>);
+const ScanKernel kScanKernels[2][2] = {{raw_scan_kernel<false, false>, raw_scan_kernel<false, true>},
+                                       {raw_scan_kernel<true, false>, raw_scan_kernel<true, true>}};
+const DlScanKernel kDlScanKernels[2][2] = {{raw_scan_dl_kernel<false, false>, raw_scan_dl_kernel<false, true>},
+                                           {raw_scan_dl_kernel<true, false>, raw_scan_dl_kernel<true, true>}};
+template <class K>
+K scan_kernel_for(const K (&instances)[2][2], const HttpRawDev& R, bool lists) {
+  return instances[lists][lds_tables_fit(R)];
 }
 
-using DlScanKernel = decltype(&raw_scan_dl_kernel<false, false>);
-DlScanKernel dl_scan_kernel_for(const HttpRawDev& R, bool lists) {
-  const bool tabs = lds_tables_fit(R);
-  if (lists) return tabs ? raw_scan_dl_kernel<true, true> : raw_scan_dl_kernel<true, false>;
-  return tabs ? raw_scan_dl_kernel<false, true> : raw_scan_dl_kernel<false, false>;
+// Workgroups of a scan kernel resident per CU with `lds` bytes of dynamic
+// LDS: what its LDS and registers allow, asked once per device, kernel and
+// size (*first: this call asked).
+int scan_blocks_per_cu(const void* kern, size_t lds, bool* first = nullptr) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, const void*, size_t>, int> occ;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = occ.find({dev, kern, lds});
+  if (first) *first = it == occ.end();
+  if (it == occ.end()) {
+    (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, kRawThreads, lds) != hipSuccess || nb < 1) nb = 1;
+    it = occ.emplace(std::make_tuple(dev, kern, lds), nb).first;
+  }
+  return it->second;
+}
+
+// A slow-path kernel (one lane per listed request, its nfields spans in LDS): two
+// workgroups per CU.  The list's count stays on the device: a small grid
+// that exits at once when the list is empty.
+template <class Kernel, class... Args>
+void launch_slow(Kernel kern, uint32_t nfields, void* stream, int cus, const Args&... args) {
+  const size_t lds = (size_t)std::max(nfields, 1u) * kRawThreads * 4;
+  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL(kern, dim3((unsigned)std::max(1, cus) * 2), dim3(kRawThreads), lds, (hipStream_t)stream, args...);
 }
 
 }  // namespace
@@ -2660,50 +2661,27 @@ DlScanKernel dl_scan_kernel_for(const HttpRawDev& R, bool lists) {
 // and registers allow (a grid past that runs a second, mostly idle round:
 // 4 requested per CU with 3 resident took 2 rounds of 475 stages per wave).
 size_t http_raw_grid(const HttpRawDev& R, bool lists, size_t n, int cus) {
-  const ScanKernel kern = scan_kernel_for(R, lists);
-  const size_t lds = raw_lds(R, http_raw_lds_keys(R), false);
-  static std::mutex mu;
-  static std::map<std::tuple<int, const void*, size_t>, int> occ;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  int per_cu = 0;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = occ.find({dev, (const void*)kern, lds});
-    if (it == occ.end()) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, kRawThreads, lds) != hipSuccess || nb < 1)
-        nb = 1;
-      it = occ.emplace(std::make_tuple(dev, (const void*)kern, lds), nb).first;
-    }
-    per_cu = it->second;
-  }
+  const int per_cu = scan_blocks_per_cu((const void*)scan_kernel_for(kScanKernels, R, lists), raw_lds(R, http_raw_lds_keys(R)));
   return grid_for(n, cus, (unsigned)per_cu);
 }
 
 bool http_raw_lds_keys(const HttpRawDev& R) { return ((size_t)R.nprogs + 2) * kRawKeys * 4 <= 32 * 1024; }
 
-int launch_http_raw_scan(const HttpRawDev& R, bool lists, const uint8_t* raw, const uint64_t* off, size_t n,
-                         const uint32_t* policy, const uint8_t* ingress, const uint16_t* port, uint32_t* counts,
-                         void* rinfo, const uint32_t* remote, uint8_t* sbuf, uint32_t cst,
-                         unsigned long long* ovf_bytes, uint32_t* dlist, uint32_t* dcount, void* stream, int cus) {
-  if (!n) return 0;
+int launch_http_raw_scan(const HttpRawDev& R, bool lists, const RawReqs& q, uint32_t* counts, void* rinfo,
+                         uint8_t* sbuf, uint32_t cst, unsigned long long* ovf_bytes, uint32_t* dlist,
+                         uint32_t* dcount, void* stream, int cus) {
+  if (!q.n) return 0;
   const bool lk = http_raw_lds_keys(R);
-  const size_t lds = raw_lds(R, lk, false);
-  const ScanKernel kern = scan_kernel_for(R, lists);
-  const unsigned grid = (unsigned)http_raw_grid(R, lists, n, cus);
+  const auto kern = scan_kernel_for(kScanKernels, R, lists);
+  const unsigned grid = (unsigned)http_raw_grid(R, lists, q.n, cus);
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kRawThreads), lds, (hipStream_t)stream, R, raw, off, n, policy, ingress,
-                     port, counts, (uint2*)rinfo, remote, sbuf, cst, ovf_bytes, (uint32_t)lk, dlist, dcount);
-  // the deferred requests (their count stays on the device: a small grid
-  // that exits at once when there are none)
-  const size_t dlds = (size_t)std::max(R.nfields, 1u) * kRawThreads * 4;
-  const auto dk = lists ? raw_defer_kernel<true> : raw_defer_kernel<false>;
-  (void)hipFuncSetAttribute((const void*)dk, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL(dk, dim3((unsigned)std::max(1, cus) * 2), dim3(kRawThreads), dlds, (hipStream_t)stream, R, raw, off,
-                     policy, ingress, port, counts, grid, (uint32_t)lk, (uint2*)rinfo, remote, sbuf, cst, ovf_bytes,
-                     (const uint32_t*)dlist, (const uint32_t*)dcount);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kRawThreads), raw_lds(R, lk), (hipStream_t)stream, R, q.raw, q.off, q.n,
+                     q.policy, q.ingress, q.port, counts, (uint2*)rinfo, q.remote, sbuf, cst, ovf_bytes, (uint32_t)lk,
+                     dlist, dcount);
+  // the deferred requests
+  launch_slow(lists ? raw_defer_kernel<true> : raw_defer_kernel<false>, R.nfields, stream, cus, R, q.raw, q.off, q.policy,
+              q.ingress, q.port, counts, grid, (uint32_t)lk, (uint2*)rinfo, q.remote, sbuf, cst, ovf_bytes,
+              (const uint32_t*)dlist, (const uint32_t*)dcount);
   return (int)hipGetLastError();
 }
 
@@ -2738,58 +2716,35 @@ int launch_http_raw_build(const HttpRawDev& R, const HttpRawRun* runs, uint32_t 
 
 // As http_raw_grid, for raw_scan_dl_kernel.
 size_t http_raw_dl_grid(const HttpRawDev& R, bool lists, size_t n, int cus) {
-  const DlScanKernel kern = dl_scan_kernel_for(R, lists);
-  const size_t lds = raw_lds(R, false, false);
-  static std::mutex mu;
-  static std::map<std::tuple<int, const void*, size_t>, int> occ;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  int per_cu = 0;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = occ.find({dev, (const void*)kern, lds});
-    if (it == occ.end()) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, kRawThreads, lds) != hipSuccess || nb < 1)
-        nb = 1;
-      it = occ.emplace(std::make_tuple(dev, (const void*)kern, lds), nb).first;
-      if (getenv("CILIUM_GPU_DEBUG"))
-        fprintf(stderr, "[cilium-gpu] raw_scan_dl_kernel<%d>: %zu B of LDS per workgroup, %d workgroups per CU\n",
-                (int)lists, lds, nb);
-    }
-    per_cu = it->second;
-  }
+  const size_t lds = raw_lds(R, false);
+  bool first = false;
+  int per_cu = scan_blocks_per_cu((const void*)scan_kernel_for(kDlScanKernels, R, lists), lds, &first);
+  if (first && getenv("CILIUM_GPU_DEBUG"))
+    fprintf(stderr, "[cilium-gpu] raw_scan_dl_kernel<%d>: %zu B of LDS per workgroup, %d workgroups per CU\n",
+            (int)lists, lds, per_cu);
   // (CILIUM_GPU_RAW_SCAN_WG: fewer workgroups per CU, for measurements)
   if (const char* v = getenv("CILIUM_GPU_RAW_SCAN_WG")) per_cu = std::max(1, std::min(per_cu, atoi(v)));
   return grid_for(n, cus, (unsigned)per_cu);
 }
 
-int launch_http_raw_dl_scan(const HttpRawDev& R, bool lists, const uint8_t* raw, const uint64_t* off, size_t n,
-                         const uint32_t* policy, const uint8_t* ingress, const uint16_t* port, const uint32_t* remote,
-                         const RawLayoutDev& L, void* stream, int cus) {
-  if (!n) return 0;
-  const size_t lds = raw_lds(R, false, false);
-  const DlScanKernel kern = dl_scan_kernel_for(R, lists);
-  const unsigned grid = (unsigned)http_raw_dl_grid(R, lists, n, cus);
+int launch_http_raw_dl_scan(const HttpRawDev& R, bool lists, const RawReqs& q, const RawLayoutDev& L, void* stream,
+                            int cus) {
+  if (!q.n) return 0;
+  const auto kern = scan_kernel_for(kDlScanKernels, R, lists);
+  const unsigned grid = (unsigned)http_raw_dl_grid(R, lists, q.n, cus);
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kRawThreads), lds, (hipStream_t)stream, R, raw, off, n, policy, ingress,
-                     port, remote, L);
-  // the deferred requests (their count stays on the device: a small grid
-  // that exits at once when there are none)
-  const size_t dlds = (size_t)std::max(R.nfields, 1u) * kRawThreads * 4;
-  const auto dk = lists ? raw_defer_dl_kernel<true> : raw_defer_dl_kernel<false>;
-  (void)hipFuncSetAttribute((const void*)dk, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL(dk, dim3((unsigned)std::max(1, cus) * 2), dim3(kRawThreads), dlds, (hipStream_t)stream, R, raw, off,
-                     policy, ingress, port, remote, L);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kRawThreads), raw_lds(R, false), (hipStream_t)stream, R, q.raw, q.off, q.n,
+                     q.policy, q.ingress, q.port, q.remote, L);
+  // the deferred requests
+  launch_slow(lists ? raw_defer_dl_kernel<true> : raw_defer_dl_kernel<false>, R.nfields, stream, cus, R, q.raw, q.off,
+              q.policy, q.ingress, q.port, q.remote, L);
   return (int)hipGetLastError();
 }
 
-bool http_raw_seal_sorts(const HttpRawDev& R) { return ((size_t)R.nprogs + 2) * 8 <= 64 * 1024; }
-
 int launch_http_raw_seal(const HttpRawDev& R, const RawLayoutDev& L, void* batch, uint32_t epoch, uint64_t ttab_off,
                          uint64_t tiles_off, uint64_t total_bytes, void* stream) {
-  const bool sort = http_raw_seal_sorts(R);
+  // the chunk table grouped by program while the groups' counts and cursors fit LDS
+  const bool sort = ((size_t)R.nprogs + 2) * 8 <= 64 * 1024;
   const size_t lds = sort ? ((size_t)R.nprogs + 2) * 8 : 0;
   (void)hipFuncSetAttribute((const void*)raw_seal_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   const unsigned pad_grid = std::max(1u, (L.nkeys + kPadThreads / 64 - 1) / (kPadThreads / 64));
@@ -2813,14 +2768,10 @@ int launch_http_ring(const HttpDev& HT, const HttpRawDev& R, const HttpRingDev& 
   return launch_http_ring_impl(HT, R, G, state, stream);
 }
 
-int launch_http_raw_walk(const HttpDev& T, const HttpRawDev& R, bool lists, const uint8_t* raw, const uint64_t* off,
-                         const uint32_t* policy, const uint8_t* ingress, const uint16_t* port, const uint32_t* remote,
-                         const RawLayoutDev& L, uint8_t* out, void* stream, int cus) {
-  const size_t lds = (size_t)std::max(R.nfields, 1u) * kRawThreads * 4;
-  const auto wk = lists ? raw_walk_kernel<true> : raw_walk_kernel<false>;
-  (void)hipFuncSetAttribute((const void*)wk, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL(wk, dim3((unsigned)std::max(1, cus) * 2), dim3(kRawThreads), lds, (hipStream_t)stream, T, R, raw,
-                     off, policy, ingress, port, remote, L, out);
+int launch_http_raw_walk(const HttpDev& T, const HttpRawDev& R, bool lists, const RawReqs& q, const RawLayoutDev& L,
+                         uint8_t* out, void* stream, int cus) {
+  launch_slow(lists ? raw_walk_kernel<true> : raw_walk_kernel<false>, R.nfields, stream, cus, T, R, q.raw, q.off, q.policy,
+              q.ingress, q.port, q.remote, L, out);
   return (int)hipGetLastError();
 }
 

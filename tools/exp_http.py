@@ -97,39 +97,34 @@ VARIANTS.update({
 })
 
 
-# Raw HTTP path (kernels_http_raw.hip): LDS stage per wave, code maps in LDS
-# (occupancy: the stage and the code maps set how many workgroups fit a CU).
+# Raw HTTP path (kernels_http_raw.hip): LDS stage per wave (occupancy: the
+# stage sets how many workgroups fit a CU).
 def _rs(stage):
     return [("kernels_http_raw.hip", "constexpr uint32_t kStage = 6144;", f"constexpr uint32_t kStage = {stage};")]
 
 
-_NOCODES = ("kernels_http_raw.hip", "return (size_t)R.nprogs * 256 <= 4 * 1024; }", "return false; }")
 VARIANTS.update({
     "raw_base": [],
     "raw_s6k": _rs(6144),
     "raw_s4k": _rs(4096),
-    "raw_nocodes": [_NOCODES],
-    "raw_s6k_nocodes": _rs(6144) + [_NOCODES],
     "raw_s5k": _rs(5120),
     "raw_s5632": _rs(5632),
     "raw_s7k": _rs(7168),
-    "raw_s5k_nocodes": _rs(5120) + [_NOCODES],
-    "raw_s5632_nocodes": _rs(5632) + [_NOCODES],
     # measuring device (verdicts meaningless, memory-safe: separators and
     # zero padding only, all valid codes): emit without the strings
-    "raw_ntstage": [("kernels_http_raw.hip", "      v = *reinterpret_cast<const uint4*>((uintptr_t)a);",
-                     "      { typedef unsigned int v4u __attribute__((ext_vector_type(4))); const v4u x = "
-                     "__builtin_nontemporal_load(reinterpret_cast<const v4u*>((uintptr_t)a)); v = make_uint4(x.x, x.y, x.z, x.w); }")],
-    "raw_nostr": [("kernels_http_raw.hip", "      for (uint32_t k = 0; k < L; k += 4) {  // a quad",
-                   "      for (uint32_t k = 0; k < 0; k += 4) {  // a quad")],
+    "raw_ntstage": [("kernels_http_raw.hip", "    S.v[j] = to_uint4(*(glb_v4*)(uintptr_t)a);",
+                     "    S.v[j] = to_uint4(__builtin_nontemporal_load((glb_v4*)(uintptr_t)a));")],
+    # (the line stands in emit_string and in emit_stage: both lose their strings)
+    "raw_nostr": [("kernels_http_raw.hip", "    for (uint32_t k = 0; k < L; k += 4) {  // a quad",
+                   "    for (uint32_t k = 0; k < 0; k += 4) {  // a quad")],
     # the scan's phases timed with the shader clock (printed by one wave)
     "raw_clocks": [("kernels_http_raw.hip", "#include <hip/hip_runtime.h>\n", "#include <hip/hip_runtime.h>\n#define CG_RAW_CLOCKS 1\n")],
     # raw_build_kernel measuring devices / variants: no class coding (verdicts
     # meaningless), nontemporal record loads, nontemporal tile stores
     "rb_nocode": [("kernels_http_raw.hip", "      c = make_uint4(code4(lut, x.x), code4(lut, x.y), code4(lut, x.z), code4(lut, x.w));",
                    "      c = x;")],
-    "rb_ntload": [("kernels_http_raw.hip", "      if (!pad && sub <= units) x = rec16[(size_t)rs + sub];",
-                   "      if (!pad && sub <= units) x = ld_nt16(rec16 + (size_t)rs + sub);")],
+    "rb_ntload": [("kernels_http_raw.hip", "      x = rec16[ok ? (size_t)rs + sub : 0];",
+                   "      x = ld_nt16(rec16 + (ok ? (size_t)rs + sub : 0));")],
     "rb_ntstore": [("kernels_http_raw.hip", "        reinterpret_cast<uint4*>(tb + 512)[(size_t)u * 64 + s] = c;",
                     "        st_nt16(reinterpret_cast<uint4*>(tb + 512) + (size_t)u * 64 + s, c);")],
     # the tile walkers' lane offset as the kernel's (spilled) copy instead of recomputed
@@ -145,8 +140,6 @@ VARIANTS.update({
                                 "__global__ __launch_bounds__(kRawThreads) void raw_scan_kernel(",
                                 "__global__ __launch_bounds__(kRawThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void raw_scan_kernel(")],
     "rank_u4": [("kernels_http_raw.hip", "constexpr uint32_t kRankU = 8;", "constexpr uint32_t kRankU = 4;")],
-    "raw_ldscodes": [("kernels_http_raw.hip", "return (size_t)R.nprogs * 256 <= 4 * 1024; }",
-                      "return (size_t)R.nprogs * 256 <= 32 * 1024; }")],
     # ipcache: addresses per lane (v4, v6)
     "ipc_v6u4": [("kernels_ipcache.hip", "constexpr uint32_t kIpcV4 = 4, kIpcV6 = 2;",
                   "constexpr uint32_t kIpcV4 = 4, kIpcV6 = 4;")],
@@ -173,8 +166,9 @@ VARIANTS.update({
     # measuring devices: the device-layout scan without its string units
     # (no code-map loads, no unit stores), and without the slot protocol (a
     # slot computed from the request index: no atomics, no directory polls)
-    "rawdl_noemit": [("kernels_http_raw.hip", "        emit_stage(R, stage, hs, sp, kRawThreads, P, last, o);",
-                      "        (void)o;")],
+    "rawdl_noemit": [("kernels_http_raw.hip", "            emit_stage(R, s.stage, s.hs, s.sp, kRawThreads, s.P, last, o);",
+                      "            (void)o;")],
+    # (the line stands in raw_scan_dl_kernel's sink and in raw_defer_dl_kernel: both take the fake slot)
     "rawdl_noslot": [("kernels_http_raw.hip",
                       "    const RawSlot sl = raw_slot(L, want, raw_vkey(L, group_of(R, prog) * kRawUnits + units, blockIdx.x), prog);",
                       "    const uint32_t tfake = (uint32_t)((i >> 6) % L.maxchunks);\n"
