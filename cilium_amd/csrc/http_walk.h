@@ -1,8 +1,12 @@
 // http_walk.h — the per-lane pieces of NetworkPolicyMap::Allowed
-// (envoy/cilium_network_policy.h:223-237) that both the verdict kernel
-// (kernels_http.hip) and the raw path's overflow walker (kernels_http_raw.hip)
-// run: a comb-table DFA step (comb.h), the accept label of a state, the
-// remote identity's PNPR mask row and the first rule two masks share.
+// (envoy/cilium_network_policy.h:223-237) that the verdict kernel
+// (kernels_http.hip), the raw path's overflow walker and the persistent ring
+// (kernels_http_raw.hip) run: a comb-table DFA step (comb.h), the accept
+// label of a state, the remote identity's PNPR mask row and the first rule
+// two masks share.  What the ring runs over its staged block is a template
+// on the type of the pointer to the program's block: const uint32_t* (global
+// memory, or LDS through a generic pointer) or const lds_u32* (LDS by
+// address space: ds_read, not flat loads).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,20 +16,36 @@
 #include "dev_types.h"
 
 namespace cg {
+
+// LDS by address space: through a generic pointer an LDS access compiles to
+// a flat load (waiting on vmcnt like an HBM load).
+#define CG_LDS __attribute__((address_space(3)))
+typedef CG_LDS uint8_t lds_u8;
+typedef CG_LDS uint32_t lds_u32;
+typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));  // (HIP's uint4 class takes no address space)
+typedef CG_LDS v4u32 lds_v4;
+__device__ __forceinline__ uint4 to_uint4(v4u32 v) { return make_uint4(v.x, v.y, v.z, v.w); }
+
 namespace walk {
 
-// One comb transition (comb.h), branch-free: every lane reads the table and
-// selects; the miss target max(S, dead) is one VALU (the walk is VALU-issue
-// bound: each wave64 instruction holds the SIMD for 4 cycles).
-// The walk is VALU-issue bound (PMC: ~60% of SIMD cycles issue VALU), so the
-// select uses SDWA word selects: compare the check half and pick the next
-// half in two instructions.  It goes through VCC, which serializes several
-// chains per lane — one chain per lane (kTilesPerWave = 1) measured fastest.
-__device__ __forceinline__ uint32_t comb_step(const uint32_t* __restrict__ cells, uint32_t dead, uint32_t st,
-                                             uint32_t b) {
-  const uint32_t e = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(cells) + ((st << 2) + (b << 2)));
+// The typed reads of a block: the cell a byte offset into it, and 16 bytes.
+__device__ __forceinline__ const uint32_t* cell_at(const uint32_t* p, uint32_t byte_off) {
+  return reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(p) + byte_off);
+}
+__device__ __forceinline__ const lds_u32* cell_at(const lds_u32* p, uint32_t byte_off) {
+  return (const lds_u32*)((const lds_u8*)p + byte_off);
+}
+__device__ __forceinline__ uint4 quad_at(const uint32_t* p) { return *reinterpret_cast<const uint4*>(p); }
+__device__ __forceinline__ uint4 quad_at(const lds_u32* p) { return to_uint4(*(const lds_v4*)p); }
+
+// nx = e.lo == st ? e.hi : max(st, dead), the select of a comb transition.
+// The walk is VALU-issue bound (PMC: ~60% of SIMD cycles issue VALU; each
+// wave64 instruction holds the SIMD for 4 cycles), so the select uses SDWA
+// word selects: compare the check half and pick the next half in two
+// instructions.  It goes through VCC, which serializes several chains per
+// lane — one chain per lane measured fastest.
+__device__ __forceinline__ uint32_t comb_select(uint32_t e, uint32_t dead, uint32_t st) {
   const uint32_t dflt = max(st, dead);
-  // nx = e.lo == st ? e.hi : dflt
   uint32_t nx;
   asm("v_cmp_eq_u32_sdwa vcc, %1, %2 src0_sel:WORD_0 src1_sel:DWORD\n\t"
       "s_nop 1\n\t"
@@ -34,53 +54,52 @@ __device__ __forceinline__ uint32_t comb_step(const uint32_t* __restrict__ cells
       : "v"(e), "v"(st), "v"(dflt)
       : "vcc");
   return nx;
+}
+
+// One comb transition (comb.h), branch-free: every lane reads the table and
+// selects; the miss target max(S, dead) is one VALU.
+template <class P>
+__device__ __forceinline__ uint32_t comb_step(P __restrict__ cells, uint32_t dead, uint32_t st, uint32_t b) {
+  return comb_select(*cell_at(cells, (st << 2) + (b << 2)), dead, st);
 }
 
 // The class-mode step (comb.h): states are byte offsets and the string
 // holds class codes 4*c, so the cell address is st + code — one SDWA add
 // with the byte select, no shift.  The block sits at LDS address 0 in the
 // fast path, so the add is the whole address.
-__device__ __forceinline__ uint32_t comb_step_cls(const uint32_t* __restrict__ cells, uint32_t dead, uint32_t st,
-                                                 uint32_t code) {
-  const uint32_t e = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(cells) + (st + code));
-  const uint32_t dflt = max(st, dead);
-  uint32_t nx;
-  asm("v_cmp_eq_u32_sdwa vcc, %1, %2 src0_sel:WORD_0 src1_sel:DWORD\n\t"
-      "s_nop 1\n\t"
-      "v_cndmask_b32_sdwa %0, %3, %1, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1"
-      : "=v"(nx)
-      : "v"(e), "v"(st), "v"(dflt)
-      : "vcc");
-  return nx;
+template <class P>
+__device__ __forceinline__ uint32_t comb_step_cls(P __restrict__ cells, uint32_t dead, uint32_t st, uint32_t code) {
+  return comb_select(*cell_at(cells, st + code), dead, st);
 }
 
-template <bool kCls>
-__device__ __forceinline__ uint32_t step(const uint32_t* __restrict__ cells, uint32_t dead, uint32_t st, uint32_t x) {
+template <bool kCls, class P>
+__device__ __forceinline__ uint32_t step(P __restrict__ cells, uint32_t dead, uint32_t st, uint32_t x) {
   return kCls ? comb_step_cls(cells, dead, st, x) : comb_step(cells, dead, st, x);
 }
 
 // Accept label of state st (its header cell).
-template <bool kCls>
-__device__ __forceinline__ uint32_t state_label(const uint32_t* __restrict__ cells, uint32_t st) {
-  return (kCls ? *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(cells) + st - 4) : cells[st - 1]) >>
-         16;
+template <bool kCls, class P>
+__device__ __forceinline__ uint32_t state_label(P __restrict__ cells, uint32_t st) {
+  return (kCls ? cell_at(cells, st)[-1] : cells[st - 1]) >> 16;
+}
+// The same with the header cell's offset worked out in 32 bits before it
+// meets the pointer, as the ring's walk reads it (the two compile to
+// different address arithmetic on a 64-bit pointer).
+template <bool kCls, class P>
+__device__ __forceinline__ uint32_t state_label32(P __restrict__ cells, uint32_t st) {
+  return *cell_at(cells, kCls ? st - 4 : 4 * (st - 1)) >> 16;
 }
 
-// Block offset of the PNPR mask of remote identity `remote`: the program's
-// remote table (open addressing, {identity, mask offset} slots).
-__device__ __forceinline__ uint32_t remote_row(const uint32_t* __restrict__ blk, const HttpProg& pg, uint32_t remote) {
-  if (pg.flags & kProgRemoteDirect) {  // uniform: the direct array (dev_types.h)
-    const uint32_t d = remote - pg.rdir_base;
-    const bool in = d < pg.rdir_len;
-    const uint32_t v = reinterpret_cast<const uint16_t*>(blk + pg.rdir_off)[in ? d : 0];
-    return in ? v : pg.default_remote;
-  }
+// Block offset of the PNPR mask of remote identity `remote` from the
+// program's remote table (open addressing, {identity, mask offset} slots).
+template <class P>
+__device__ __forceinline__ uint32_t remote_row_hashed(P __restrict__ blk, const HttpProg& pg, uint32_t remote) {
   // both candidate buckets read together (dev_types.h rtab_b1/rtab_b2)
   const uint32_t h = rtab_hash(remote);
-  const uint32_t* b1 = blk + pg.rtab_off + kRtabBucketCells * rtab_b1h(h, pg.rtab_nb);
-  const uint32_t* b2 = blk + pg.rtab_off + kRtabBucketCells * rtab_b2h(h, pg.rtab_nb);
-  const uint4 k1 = *reinterpret_cast<const uint4*>(b1), k2 = *reinterpret_cast<const uint4*>(b2);
-  const uint4 r1 = *reinterpret_cast<const uint4*>(b1 + 4), r2 = *reinterpret_cast<const uint4*>(b2 + 4);
+  const P b1 = blk + pg.rtab_off + kRtabBucketCells * rtab_b1h(h, pg.rtab_nb);
+  const P b2 = blk + pg.rtab_off + kRtabBucketCells * rtab_b2h(h, pg.rtab_nb);
+  const uint4 k1 = quad_at(b1), k2 = quad_at(b2);
+  const uint4 r1 = quad_at(b1 + 4), r2 = quad_at(b2 + 4);
   // an empty slot holds an identity outside the table with the default row
   uint32_t row = pg.default_remote;
   row = k1.x == remote ? r1.x : row;
@@ -92,6 +111,19 @@ __device__ __forceinline__ uint32_t remote_row(const uint32_t* __restrict__ blk,
   row = k2.z == remote ? r2.z : row;
   row = k2.w == remote ? r2.w : row;
   return row;
+}
+
+// The same for any program: from its direct array when it has one, else from
+// the remote table.  (The ring reads the direct array through its own typed
+// pointer, kernels_http_raw.hip ring_remote_row.)
+__device__ __forceinline__ uint32_t remote_row(const uint32_t* __restrict__ blk, const HttpProg& pg, uint32_t remote) {
+  if (pg.flags & kProgRemoteDirect) {  // uniform: the direct array (dev_types.h)
+    const uint32_t d = remote - pg.rdir_base;
+    const bool in = d < pg.rdir_len;
+    const uint32_t v = reinterpret_cast<const uint16_t*>(blk + pg.rdir_off)[in ? d : 0];
+    return in ? v : pg.default_remote;
+  }
+  return remote_row_hashed(blk, pg, remote);
 }
 
 // u64 word w of the block mask at block offset a (u32 units, 8-byte aligned).
@@ -119,6 +151,19 @@ __device__ __forceinline__ uint32_t first_meet_w(const uint32_t* __restrict__ bl
     base = nz ? 64u * w : base;
   }
   return sel ? base + (uint32_t)__builtin_ctzll(sel) : kNoHit;
+}
+
+// The same by a plain loop over the words, each read as two cells, leaving
+// at the first word with a shared bit: any W and any pointer type (the
+// ring's; first_meet's default branch reads whole words).
+template <class P>
+__device__ __forceinline__ uint32_t first_meet_loop(P __restrict__ blk, uint32_t a, uint32_t row, uint32_t W) {
+  for (uint32_t w = 0; w < W; ++w) {
+    const unsigned long long x = ((unsigned long long)*(blk + a + 2 * w + 1) << 32 | *(blk + a + 2 * w)) &
+                                 ((unsigned long long)*(blk + row + 2 * w + 1) << 32 | *(blk + row + 2 * w));
+    if (x) return w * 64 + (uint32_t)__builtin_ctzll(x);
+  }
+  return kNoHit;
 }
 
 __device__ __forceinline__ uint32_t first_meet(const uint32_t* __restrict__ blk, uint32_t a, uint32_t row,

@@ -113,15 +113,10 @@ constexpr uint32_t kAbsentSpan = 0xFFFFFFFFu;
 
 // Explicit address spaces for the scan's LDS stage, bitmaps, spans and tables
 // and for the heads in HBM: through generic pointers every stage access
-// compiled to a flat load (waiting on vmcnt like an HBM load).
-#define CG_LDS __attribute__((address_space(3)))
+// compiled to a flat load (waiting on vmcnt like an HBM load).  The LDS
+// types (CG_LDS, lds_u8, lds_u32, lds_v4, to_uint4) are http_walk.h's.
 #define CG_GLB __attribute__((address_space(1)))
-typedef CG_LDS uint8_t lds_u8;
-typedef CG_LDS uint32_t lds_u32;
-typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));  // (HIP's uint4 class takes no address space)
-typedef CG_LDS v4u32 lds_v4;
 typedef const CG_GLB v4u32 glb_v4;
-__device__ __forceinline__ uint4 to_uint4(v4u32 v) { return make_uint4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ v4u32 to_v4(uint4 v) { return v4u32{v.x, v.y, v.z, v.w}; }
 typedef const CG_GLB uint8_t glb_u8;
 typedef const CG_GLB uint32_t glb_u32;
@@ -2238,26 +2233,6 @@ __device__ __forceinline__ void ring_masks(const lds_u8* blob, uint32_t bytes, c
 // the next four bytes and their codes loaded ahead of this four's steps, so
 // only the cell load is on the chain.  Cells and codes are LDS pointers
 // when the program is staged (ds_read, not flat loads).
-__device__ __forceinline__ uint32_t ring_cell(const lds_u32* cells, uint32_t byte_off) {
-  return *(const lds_u32*)((const lds_u8*)cells + byte_off);
-}
-__device__ __forceinline__ uint32_t ring_cell(const uint32_t* cells, uint32_t byte_off) {
-  return *(const uint32_t*)((const uint8_t*)cells + byte_off);
-}
-template <bool kCls, class CellP>
-__device__ __forceinline__ uint32_t ring_step(CellP cells, uint32_t dead, uint32_t st, uint32_t x) {
-  // walk::comb_step / comb_step_cls on the typed pointer
-  const uint32_t e = ring_cell(cells, kCls ? st + x : (st << 2) + (x << 2));
-  const uint32_t dflt = max(st, dead);
-  uint32_t nx;
-  asm("v_cmp_eq_u32_sdwa vcc, %1, %2 src0_sel:WORD_0 src1_sel:DWORD\n\t"
-      "s_nop 1\n\t"
-      "v_cndmask_b32_sdwa %0, %3, %1, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1"
-      : "=v"(nx)
-      : "v"(e), "v"(st), "v"(dflt)
-      : "vcc");
-  return nx;
-}
 template <bool kCls, class CellP, class CodeP>
 __device__ __forceinline__ uint32_t ring_run(const HttpRawDev& R, CellP cells, uint32_t dead, uint32_t st, CodeP lut,
                                              const lds_u8* blob, uint32_t hs, const lds_u32* sp, const Parsed& P,
@@ -2267,8 +2242,8 @@ __device__ __forceinline__ uint32_t ring_run(const HttpRawDev& R, CellP cells, u
   for (uint32_t rem = P.present; rem && st != dead; rem &= rem - 1) {
     const uint32_t g = (uint32_t)__builtin_ctz(rem);
     for (; f < g && st != dead; ++f) {
-      st = ring_step<kCls>(cells, dead, st, c_abs);
-      st = st == dead ? st : ring_step<kCls>(cells, dead, st, c_sep);
+      st = walk::step<kCls>(cells, dead, st, c_abs);
+      st = st == dead ? st : walk::step<kCls>(cells, dead, st, c_sep);
     }
     const uint32_t sv = sp[g * kRingThreads], a = hs + (sv >> 16), L = sv & 0xFFFFu;
     uint32_t w = squad(blob, a), k = 0;
@@ -2281,22 +2256,20 @@ __device__ __forceinline__ uint32_t ring_run(const HttpRawDev& R, CellP cells, u
 #pragma unroll
       for (int j = 0; j < 4; ++j) x[j] = lut[(w >> (8 * j)) & 0xFFu];
 #pragma unroll
-      for (uint32_t j = 0; j < 4; ++j) st = ring_step<kCls>(cells, dead, st, x[j]);
+      for (uint32_t j = 0; j < 4; ++j) st = walk::step<kCls>(cells, dead, st, x[j]);
       w = wn;
     }
-    for (uint32_t j = 0; k + j < L && st != dead; ++j) st = ring_step<kCls>(cells, dead, st, (uint32_t)lut[(w >> (8 * j)) & 0xFFu]);
-    st = st == dead ? st : ring_step<kCls>(cells, dead, st, c_sep);
+    for (uint32_t j = 0; k + j < L && st != dead; ++j) st = walk::step<kCls>(cells, dead, st, (uint32_t)lut[(w >> (8 * j)) & 0xFFu]);
+    st = st == dead ? st : walk::step<kCls>(cells, dead, st, c_sep);
     f = g + 1;
   }
-  if (last < R.nfields && st != dead) st = ring_step<kCls>(cells, dead, st, (uint32_t)lut[2]);  // REST
+  if (last < R.nfields && st != dead) st = walk::step<kCls>(cells, dead, st, (uint32_t)lut[2]);  // REST
   return st;
 }
-// walk::remote_row / state_label / first_meet over a typed block pointer
-// (LDS when staged: ds_read, not flat loads).
-__device__ __forceinline__ uint4 ring_q(const lds_u32* p) { return to_uint4(*(const lds_v4*)p); }
-__device__ __forceinline__ uint4 ring_q(const uint32_t* p) { return *(const uint4*)p; }
-__device__ __forceinline__ uint32_t ring_w(const lds_u32* p) { return *p; }
-__device__ __forceinline__ uint32_t ring_w(const uint32_t* p) { return *p; }
+// walk::remote_row over a typed block pointer (LDS when staged: ds_read, not
+// flat loads).  Only the direct array's halfword read is the ring's own: read
+// the way walk::remote_row reads it, the ring kernels compile to other code
+// (DESIGN 3.9.1); the remote table's lookup is walk::remote_row_hashed.
 __device__ __forceinline__ uint32_t ring_h(const lds_u32* p, uint32_t i) { return ((const CG_LDS uint16_t*)p)[i]; }
 __device__ __forceinline__ uint32_t ring_h(const uint32_t* p, uint32_t i) { return ((const uint16_t*)p)[i]; }
 template <class CellP>
@@ -2307,29 +2280,7 @@ __device__ __forceinline__ uint32_t ring_remote_row(CellP blk, const HttpProg& p
     const uint32_t v = ring_h(blk + pg.rdir_off, in ? d : 0);
     return in ? v : pg.default_remote;
   }
-  const uint32_t h = rtab_hash(remote);
-  const CellP b1 = blk + pg.rtab_off + kRtabBucketCells * rtab_b1h(h, pg.rtab_nb);
-  const CellP b2 = blk + pg.rtab_off + kRtabBucketCells * rtab_b2h(h, pg.rtab_nb);
-  const uint4 k1 = ring_q(b1), k2 = ring_q(b2), r1 = ring_q(b1 + 4), r2 = ring_q(b2 + 4);
-  uint32_t row = pg.default_remote;
-  row = k1.x == remote ? r1.x : row;
-  row = k1.y == remote ? r1.y : row;
-  row = k1.z == remote ? r1.z : row;
-  row = k1.w == remote ? r1.w : row;
-  row = k2.x == remote ? r2.x : row;
-  row = k2.y == remote ? r2.y : row;
-  row = k2.z == remote ? r2.z : row;
-  row = k2.w == remote ? r2.w : row;
-  return row;
-}
-template <class CellP>
-__device__ __forceinline__ uint32_t ring_first_meet(CellP blk, uint32_t a, uint32_t row, uint32_t W) {
-  for (uint32_t w = 0; w < W; ++w) {
-    const unsigned long long x = ((unsigned long long)ring_w(blk + a + 2 * w + 1) << 32 | ring_w(blk + a + 2 * w)) &
-                                 ((unsigned long long)ring_w(blk + row + 2 * w + 1) << 32 | ring_w(blk + row + 2 * w));
-    if (x) return w * 64 + (uint32_t)__builtin_ctzll(x);
-  }
-  return walk::kNoHit;
+  return walk::remote_row_hashed(blk, pg, remote);
 }
 // walk_request_at from the parsed spans over the program's block and code
 // map at blk / lut (LDS, staged, or global memory); pt0: its first part.
@@ -2350,10 +2301,10 @@ __device__ __forceinline__ uint32_t walk_spans_at(const HttpDev& T, const HttpRa
       if (!(pg.flags & kProgRebased)) cells = T.cells + pt.walk_off;
     const uint32_t st = cls ? ring_run<true>(R, cells, pt.dead, pt.start, lut, blob, hs, sp, P, last)
                             : ring_run<false>(R, cells, pt.dead, pt.start, lut, blob, hs, sp, P, last);
-    const uint32_t lab = (cls ? ring_cell(cells, st - 4) : ring_cell(cells, 4 * (st - 1))) >> 16;
-    if (lab != 0xFFFFu) hit = min(hit, ring_first_meet(blk, pt.acc_off + lab * 2 * W, row, W));
+    const uint32_t lab = cls ? walk::state_label32<true>(cells, st) : walk::state_label32<false>(cells, st);
+    if (lab != 0xFFFFu) hit = min(hit, walk::first_meet_loop(blk, pt.acc_off + lab * 2 * W, row, W));
   }
-  if (pg.flags & kProgHasAlways) hit = min(hit, ring_first_meet(blk, pg.always_off, row, W));
+  if (pg.flags & kProgHasAlways) hit = min(hit, walk::first_meet_loop(blk, pg.always_off, row, W));
   return hit;
 }
 

@@ -15,42 +15,16 @@ sys.path.insert(0, str(ROOT))
 from cilium_amd import build as B  # noqa: E402
 
 OUT = ROOT / "tools" / "_exp"
-# Substitutions on the current kernels_http.hip.  Variants are measuring
-# devices; "nowalk" breaks the verdicts on purpose (memory-safe: the walk
-# result stays live but never indexes the accept tables).
-WALK_N = """#pragma unroll
-  for (int k = 0; k < N; ++k) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) st = comb_step(blk, self_lo, st, get_byte(unit[k], i));
-  }"""
-NOWALK = (WALK_N, """#pragma unroll
-  for (int k = 0; k < N; ++k) asm volatile("" ::"v"(unit[k].x), "v"(unit[k].y), "v"(unit[k].z), "v"(unit[k].w));""")
-EARLY = (WALK_N, """#pragma unroll
-  for (int k = 0; k < N; ++k) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) st = comb_step(blk, self_lo, st, get_byte(unit[k], i));
-    if (k + 1 < N && !__any(st != 0)) break;
-  }""")
-NOCTR = ("""  count_hits(T, pg, hit, s_hits, lane);
-  out[(size_t)t * kWave + lane] = (uint8_t)verdict;""", """  out[(size_t)t * kWave + lane] = (uint8_t)verdict;""")
+# Substitutions on the current sources (tests/test_exp_variants.py checks that
+# every old text still occurs).  Variants are measuring devices; "h_nowalk"
+# breaks the verdicts on purpose (memory-safe: the walk result stays live but
+# never indexes the accept tables).
 VARIANTS = {
     "base": [],
-    "nosort": [("http_pack.cc", "  if (build) {\n    // each bucket sorted as", "  if (false) {\n    // each bucket sorted as")],
-    "lensort": [("http_pack.cc", "        if (a.pre[0] != b.pre[0]) return a.pre[0] < b.pre[0];",
-                 "        if (a.len != b.len) return a.len < b.len;\n        if (a.pre[0] != b.pre[0]) return a.pre[0] < b.pre[0];")],
 }
-# Kafka wire decode variants (kernels_kafka.hip): thread count / LDS stage.
-def _kw(threads, stage):
-    return [("kernels_kafka.hip", "constexpr uint32_t kKwThreads = 256;", f"constexpr uint32_t kKwThreads = {threads};"),
-            ("kernels_kafka.hip", "constexpr uint32_t kKwStage = 4096;", f"constexpr uint32_t kKwStage = {stage};")]
-
-
+# Kafka wire decode variants (kernels_kafka.hip).
 VARIANTS.update({
     "kw_base": [],
-    "kw_t256_s4k": _kw(256, 4096),
-    "kw_t256_s2k": _kw(256, 2048),
-    "kw_nostage": _kw(256, 0),
-    "kw_nostage_t128": _kw(128, 0),
     "kw_nocrc": [("kernels_kafka.hip", "    uint32_t c = 0xFFFFFFFFu;\n    uint32_t h = (4u",
                   "    if (n > 0) return p[0];\n    uint32_t c = 0xFFFFFFFFu;\n    uint32_t h = (4u")],
 })
@@ -62,36 +36,29 @@ def _l4t(k):
     return [("kernels.hip", "constexpr uint32_t kL4Tuples = 4;", f"constexpr uint32_t kL4Tuples = {k};")]
 
 
-_NOPIPE = ("kernels.hip", "constexpr bool kL4Pipe = true;", "constexpr bool kL4Pipe = false;")
+_PIPE = ("kernels.hip", "constexpr bool kL4Pipe = false;", "constexpr bool kL4Pipe = true;")
 VARIANTS.update({
-    "l4_pipe4": _l4t(4),
-    "l4_pipe8": _l4t(8),
-    "l4_nopipe4": _l4t(4) + [_NOPIPE],
-    "l4_nopipe8": _l4t(8) + [_NOPIPE],
+    "l4_pipe4": _l4t(4) + [_PIPE],
+    "l4_pipe8": _l4t(8) + [_PIPE],
+    "l4_nopipe4": _l4t(4),
+    "l4_nopipe8": _l4t(8),
     "l4_noctr": [("kernels.hip", "      if (which) l4_count(t, lcnt, val & 0xFFFF, w[u][2]);", "")],
     # prefilter: addresses per lane (v4, v6)
-    "lpm_4_2": [("kernels.hip", "constexpr uint32_t kLpmV4 = 4, kLpmV6 = 2;", "constexpr uint32_t kLpmV4 = 4, kLpmV6 = 2;")],
-    "lpm_8_4": [("kernels.hip", "constexpr uint32_t kLpmV4 = 4, kLpmV6 = 2;", "constexpr uint32_t kLpmV4 = 8, kLpmV6 = 4;")],
-    "lpm_4_4": [("kernels.hip", "constexpr uint32_t kLpmV4 = 4, kLpmV6 = 2;", "constexpr uint32_t kLpmV4 = 4, kLpmV6 = 4;")],
+    "lpm_4_2": [("kernels.hip", "constexpr uint32_t kLpmV4 = 8, kLpmV6 = 2;", "constexpr uint32_t kLpmV4 = 4, kLpmV6 = 2;")],
+    "lpm_8_4": [("kernels.hip", "constexpr uint32_t kLpmV4 = 8, kLpmV6 = 2;", "constexpr uint32_t kLpmV4 = 8, kLpmV6 = 4;")],
+    "lpm_4_4": [("kernels.hip", "constexpr uint32_t kLpmV4 = 8, kLpmV6 = 2;", "constexpr uint32_t kLpmV4 = 4, kLpmV6 = 4;")],
     # HTTP: dynamic (ticket) vs static chunk dealing
     "h_dyn": [],
     "h_static": [("constexpr bool kDynamicDeal = true;", "constexpr bool kDynamicDeal = false;")],
     # occupancy vs spills: 8 waves/SIMD caps VGPRs at 64 (40 B/lane of scratch)
-    "h_w7": [("amdgpu_waves_per_eu(8, 8)", "amdgpu_waves_per_eu(7, 8)")],
-    "h_w6": [("amdgpu_waves_per_eu(8, 8)", "amdgpu_waves_per_eu(6, 8)")],
+    "h_w7": [("amdgpu_waves_per_eu(kHttpWaves, kHttpWaves)", "amdgpu_waves_per_eu(7, kHttpWaves)")],
+    "h_w6": [("amdgpu_waves_per_eu(kHttpWaves, kHttpWaves)", "amdgpu_waves_per_eu(6, kHttpWaves)")],
     # next-tile prefetch depth and the rolling unit window
     "h_pre2": [("constexpr int kPre = 1;", "constexpr int kPre = 2;")],
     "h_win2": [("constexpr int kWin = N < 4 ? (N > 0 ? N : 1) : 4;", "constexpr int kWin = N < 2 ? (N > 0 ? N : 1) : 2;")],
     "h_win3": [("constexpr int kWin = N < 4 ? (N > 0 ? N : 1) : 4;", "constexpr int kWin = N < 3 ? (N > 0 ? N : 1) : 3;")],
     # nontemporal meta / prefetched-unit loads off (the in-walk unit loads stay nontemporal)
     "h_nt_units_only": [("#define NT_META(p) ld_nt(p)\n#define NT_PRE(p) ld_nt(p)", "#define NT_META(p) (*(p))\n#define NT_PRE(p) (*(p))")],
-    "h_ntout": [("  out[(size_t)t * kWave + lane] = (uint8_t)verdict;\n  n_allow += counted && verdict;",
-                 "  __builtin_nontemporal_store((uint8_t)verdict, out + (size_t)t * kWave + lane);\n  n_allow += counted && verdict;")],
-    "h_old": [("#define NT_META(p) ld_nt(p)\n#define NT_PRE(p) ld_nt(p)", "#define NT_META(p) (*(p))\n#define NT_PRE(p) (*(p))"),
-              ("unit[k] = k < kPre ? cur.u[k < kPre ? k : 0] : ld_nt(tr.units + k * kWave + lane);",
-               "unit[k] = k < kPre ? cur.u[k < kPre ? k : 0] : tr.units[k * kWave + lane];"),
-              ("unit[k % kWin] = ld_nt(tr.units + (k + kWin) * kWave + lane);",
-               "unit[k % kWin] = tr.units[(k + kWin) * kWave + lane];")],
     "h_nt_nometa": [("#define NT_META(p) ld_nt(p)", "#define NT_META(p) (*(p))")],
     "h_win6": [("constexpr int kWin = N < 4 ? (N > 0 ? N : 1) : 4;", "constexpr int kWin = N < 6 ? (N > 0 ? N : 1) : 6;")],
 })
@@ -140,11 +107,6 @@ VARIANTS.update({
                                 "__global__ __launch_bounds__(kRawThreads) void raw_scan_kernel(",
                                 "__global__ __launch_bounds__(kRawThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void raw_scan_kernel(")],
     "rank_u4": [("kernels_http_raw.hip", "constexpr uint32_t kRankU = 8;", "constexpr uint32_t kRankU = 4;")],
-    # ipcache: addresses per lane (v4, v6)
-    "ipc_v6u4": [("kernels_ipcache.hip", "constexpr uint32_t kIpcV4 = 4, kIpcV6 = 2;",
-                  "constexpr uint32_t kIpcV4 = 4, kIpcV6 = 4;")],
-    "ipc_v4u8": [("kernels_ipcache.hip", "constexpr uint32_t kIpcV4 = 4, kIpcV6 = 2;",
-                  "constexpr uint32_t kIpcV4 = 8, kIpcV6 = 2;")],
     # round 5 measuring devices on the class-mode walker (verdicts meaningless;
     # every LDS address stays inside the block or reads LDS out of range as 0):
     # the DFA step without its LDS read (same VALU count), and no walk at all
@@ -153,11 +115,6 @@ VARIANTS.update({
     "h_nowalk": [('  if (B == 0) CG_CLS_STEP("BYTE_0");',
                   '  if (true) {\n    asm volatile("v_mov_b32 %0, %1" : "=v"(nx) : "v"(st), "v"(w));\n    return nx;\n  }\n'
                   '  if (B == 0) CG_CLS_STEP("BYTE_0");')],
-    # two tiles per wave, one request of each per lane, two LDS chains
-    # (lds_cls_step2); h_pair_w1: a one-unit rolling window per chain
-    "h_pair": [("constexpr bool kPairTiles = false;", "constexpr bool kPairTiles = true;")],
-    "h_pair_w1": [("constexpr bool kPairTiles = false;", "constexpr bool kPairTiles = true;"),
-                  ("  constexpr int kW = N < 2 ? (N > 0 ? N : 1) : 2;", "  constexpr int kW = 1;")],
     # measuring device: the device-layout scan's string units written
     # uncoded (no per-byte code-map loads; verdicts meaningless)
     "rawdl_nocode": [("raw_emit.h", "CG_HD inline uint32_t code4(const uint8_t* lut, uint32_t q) {\n  return",
@@ -192,12 +149,7 @@ VARIANTS.update({
                ("  if (has_next) tile_prefetch(trn, nunits, lane, nxt);\n  __builtin_amdgcn_sched_barrier(0);",
                 "  if (has_next) tile_prefetch(trn, nunits, lane, nxt);\n  __builtin_amdgcn_s_setprio(0);\n  __builtin_amdgcn_sched_barrier(0);")],
     # 4 waves per SIMD (128 VGPRs, one 1024-thread workgroup per CU): the
-    # registers spent on a second chain (pairs) and / or deeper prefetch
-    "h_pair_w4": [("constexpr bool kPairTiles = false;", "constexpr bool kPairTiles = true;"),
-                  ("constexpr int kHttpWaves = 8;", "constexpr int kHttpWaves = 4;")],
-    "h_pair_w4_pre2": [("constexpr bool kPairTiles = false;", "constexpr bool kPairTiles = true;"),
-                       ("constexpr int kHttpWaves = 8;", "constexpr int kHttpWaves = 4;"),
-                       ("constexpr int kPre = 1;", "constexpr int kPre = 2;")],
+    # registers spent on deeper prefetch
     "h_w4_pre4": [("constexpr int kHttpWaves = 8;", "constexpr int kHttpWaves = 4;"),
                   ("constexpr int kPre = 1;", "constexpr int kPre = 4;")],
     # the scans at 512 threads per workgroup (spans / tables amortized over 8
