@@ -19,8 +19,10 @@
 #include "kafka_wire.h"
 #include "kernels.h"
 #include "l4.h"
+#include "l4_walk.h"
 #include "ipcache.h"
 #include "lpm.h"
+#include "lpm_walk.h"
 #include "regex.h"
 #include "ring.h"
 #include "selcache.h"
@@ -868,7 +870,7 @@ int cg_diag_ipcache_eval_host(uint64_t h, uint32_t ipc_id, const uint32_t* v4, s
           v = xv;  // a /128 entry
         } else {
           v = t.runs6[4 * (size_t)R + 2];
-          if (!ipc_le128(t.runs6[4 * (size_t)R], t.runs6[4 * (size_t)R + 1], hi, lo))
+          if (!le128(t.runs6[4 * (size_t)R], t.runs6[4 * (size_t)R + 1], hi, lo))
             v = ipc_v6_search_value(t, hi, lo, L, R, crowd);
         }
       }
@@ -2244,48 +2246,31 @@ int cg_diag_http_eval_host(uint64_t h, const void* batch, size_t nslots, const u
   });
 }
 
-// Cuckoo lookup as the L4 kernels do it: fingerprint screen, then the slot.
-static bool l4_lookup_host(const PolicyMapState& m, uint64_t key, uint32_t* val) {
-  uint32_t b1, b2, fp;
-  l4_place(key, m.bucket_mask, &b1, &b2, &fp);
-  for (uint32_t bk : {b1, b2}) {
-    const L4Slot* b = m.slots.data() + (size_t)bk * 4;
-    for (int s = 0; s < 4; ++s)
-      if (((m.fp[bk] >> (8 * s)) & 0xFF) == fp && b[s].key == key) {
-        *val = b[s].val;
-        return true;
-      }
-  }
-  return false;
-}
+// The L4, prefilter and Kafka host evaluators run the kernels' own per-item
+// functions (l4_walk.h, lpm_walk.h, kafka_walk.h) over host_view(), each item
+// loaded as the kernel's load phases load it.
 
+// Per tuple as l4_kernel does it, with plain CG_L4_CAN_ACCESS semantics.
 int cg_diag_l4_eval_host(uint64_t h, uint32_t map_id, const cg_l4_tuple* t, size_t n, int32_t* out) {
   return guarded([&] {
     auto e = get(h);
     std::lock_guard<std::mutex> lk(e->mu);
     PolicyMapState& m = get_map(*e, map_id);
     if (m.dirty) m.rebuild(*e);
+    const L4Dev T = m.host_view();
     for (size_t i = 0; i < n; ++i) {
-      const bool frag = t[i].flags & CG_L4_F_FRAGMENT;
-      const uint64_t eg = (t[i].flags & CG_L4_F_INGRESS) ? 0 : 1;
+      uint32_t w[3];  // identity, dport | proto << 16 | flags << 24, len
+      memcpy(w, &t[i], sizeof(w));
+      const uint32_t w1 = l4_mode_word(w[1], CG_L4_CAN_ACCESS);
       uint32_t val = 0;
-      int which = 0;
-      if (!frag && l4_lookup_host(m, (uint64_t)t[i].identity | ((uint64_t)t[i].dport << 32) |
-                                         ((uint64_t)t[i].proto << 48) | (eg << 56), &val))
-        which = 1;
-      else if (l4_lookup_host(m, (uint64_t)t[i].identity | (eg << 56), &val))
-        which = 2;
-      else if (!frag && l4_lookup_host(m, ((uint64_t)t[i].dport << 32) | ((uint64_t)t[i].proto << 48) | (eg << 56),
-                                       &val))
-        which = 3;
-      if (which == 1 || which == 3) out[i] = (int32_t)(val >> 16);
-      else if (which == 2 || (t[i].flags & CG_L4_F_CB_POLICY)) out[i] = 0;
-      else out[i] = frag ? CG_DROP_FRAG_NOSUPPORT : CG_DROP_POLICY;
+      const int which = l4_resolve(T, [&](uint32_t b) { return T.fp[b]; }, w[0], w1,
+                                   (w1 >> 24) & CG_L4_F_FRAGMENT, &val);
+      out[i] = l4_wrap(l4_verdict(which, val, w1 >> 24), CG_L4_CAN_ACCESS);
     }
   });
 }
 
-// The prefilter tables walked exactly as lpm_kernel does.
+// Per packet as lpm_kernel does it.
 int cg_diag_prefilter_eval_host(uint64_t h, uint32_t pf_id, const uint32_t* v4, size_t n4, uint8_t* out4,
                                 const uint8_t* v6, size_t n6, uint8_t* out6) {
   return guarded([&] {
@@ -2293,74 +2278,34 @@ int cg_diag_prefilter_eval_host(uint64_t h, uint32_t pf_id, const uint32_t* v4, 
     std::lock_guard<std::mutex> lk(e->mu);
     PrefilterState& p = get_pf(*e, pf_id);
     if (p.dirty) p.rebuild(*e);
-    auto ep4 = [&](uint32_t a) {
-      if (a == 0) return p.ep4_zero;
-      uint32_t mask = (uint32_t)p.ep4_keys.size() - 1, hh = ep_hash32(a) & mask;
-      for (uint32_t k = 0; k <= mask; ++k, hh = (hh + 1) & mask) {
-        if (p.ep4_keys[hh] == a) return true;
-        if (p.ep4_keys[hh] == 0) return false;
-      }
-      return false;
-    };
-    auto ep6 = [&](uint64_t hi, uint64_t lo) {
-      if ((hi | lo) == 0) return p.ep6_zero;
-      uint32_t mask = (uint32_t)(p.ep6_keys.size() / 2) - 1, hh = ep_hash128(hi, lo) & mask;
-      for (uint32_t k = 0; k <= mask; ++k, hh = (hh + 1) & mask) {
-        if (p.ep6_keys[2 * hh] == hi && p.ep6_keys[2 * hh + 1] == lo) return true;
-        if ((p.ep6_keys[2 * hh] | p.ep6_keys[2 * hh + 1]) == 0) return false;
-      }
-      return false;
-    };
-    auto be64 = [](const uint8_t* a) {
-      uint64_t x = 0;
-      for (int i = 0; i < 8; ++i) x = x << 8 | a[i];
-      return x;
-    };
+    const LpmDev t = p.host_view();
+    const bool v4f = p.v4_filter, v6f = p.v6_filter;  // as the launch passes them
     for (size_t i = 0; i < n4; ++i) {
-      uint32_t s = __builtin_bswap32(v4[2 * i]);
-      bool drop = false;
-      if (p.v4_filter) {
-        const uint32_t q = s >> 16, tw = p.top[q >> 4], tc = (tw >> (2 * (q & 15))) & 3;
-        if (tc == kLpmPartial) {
-          const uint32_t m = p.top_rank[q >> 4] + __builtin_popcount(lpm_partials(tw) & ((1u << (2 * (q & 15))) - 1));
-          const uint32_t k = (s >> 8) & 255, w = p.mid[(size_t)m * 16 + (k >> 4)], c = (w >> (2 * (k & 15))) & 3;
-          if (c == kLpmPartial) {
-            uint32_t rank = p.leaf_base[m];
-            for (uint32_t j = 0; j < (k >> 4); ++j) rank += __builtin_popcount(lpm_partials(p.mid[(size_t)m * 16 + j]));
-            rank += __builtin_popcount(lpm_partials(w) & ((1u << (2 * (k & 15))) - 1));
-            drop = (p.leaves[(size_t)rank * 4 + ((s & 0xFF) >> 6)] >> (s & 63)) & 1;
-          } else {
-            drop = c == 1;
-          }
-        } else {
-          drop = tc == 1;
-        }
-      }
-      if (!drop) drop = !ep4(v4[2 * i + 1]);
+      const uint32_t s = __builtin_bswap32(v4[2 * i]), a = v4[2 * i + 1];
+      const uint32_t w = v4f ? t.top[s >> 20] : 0u;
+      const uint32_t eh = ep_hash32(a) & t.ep4_mask, ek = t.ep4_keys[eh];
+      bool drop = v4_covered(t, s, w);
+      if (!drop) drop = !ep4_has(t, a, ek, eh);
       out4[i] = drop ? CG_XDP_DROP : CG_XDP_PASS;
     }
     for (size_t i = 0; i < n6; ++i) {
-      uint64_t hi = be64(v6 + 32 * i), lo = be64(v6 + 32 * i + 8);
-      bool drop = false;
-      if (p.v6_filter) {
-        const uint32_t t = (uint32_t)(hi >> (64 - p.v6_bits));
-        uint32_t m;
-        const uint32_t code = v6_code_of(p.v6_code[t >> 4], t, &m);
-        drop = code == 1;
-        if (code == kLpmPartial) {
-          const uint32_t e = p.v6_mix[m], span = e & 15;
-          int64_t R = e >> 4, L = span == 15 ? 0 : R - span;
-          int64_t ans = -1;
-          while (L <= R) {
-            int64_t mid = (L + R) >> 1;
-            std::pair<uint64_t, uint64_t> lo_m{p.v6_iv[4 * mid], p.v6_iv[4 * mid + 1]};
-            if (!(std::make_pair(hi, lo) < lo_m)) ans = mid, L = mid + 1;
-            else R = mid - 1;
-          }
-          drop = ans >= 0 && !(std::make_pair(p.v6_iv[4 * ans + 2], p.v6_iv[4 * ans + 3]) < std::make_pair(hi, lo));
-        }
-      }
-      if (!drop) drop = !ep6(be64(v6 + 32 * i + 16), be64(v6 + 32 * i + 24));
+      const uint4 a = load16(v6 + 32 * i), b = load16(v6 + 32 * i + 16);
+      const uint64_t sh = __builtin_bswap64(u64_of(a.x, a.y)), sl = __builtin_bswap64(u64_of(a.z, a.w));
+      const uint64_t dh = __builtin_bswap64(u64_of(b.x, b.y)), dl = __builtin_bswap64(u64_of(b.z, b.w));
+      const uint64_t cw = v6f ? t.v6_code[sh >> (68 - t.v6_bits)] : 0;
+      const uint32_t eh = ep_hash128(dh, dl) & t.ep6_mask;
+      const uint4 ek = load16(t.ep6_keys + 2 * (size_t)eh);
+      // level 2, then the top two candidates of a mixed bucket
+      uint32_t m;
+      const uint32_t code = v6_code_of(cw, (uint32_t)(sh >> (64 - t.v6_bits)), &m);
+      const bool mixed = code == kLpmPartial;
+      const V6Window win = v6_window(t.v6_mix[mixed ? m : 0], mixed);
+      const int64_t r1 = mixed ? win.R : 0, r0 = mixed && win.R - 1 >= win.L ? win.R - 1 : r1;
+      bool drop = code == 1;
+      if (mixed)
+        drop = v6_covered(t, sh, sl, win, load16(t.v6_iv + 4 * r1), load16(t.v6_iv + 4 * r1 + 2),
+                          load16(t.v6_iv + 4 * r0), load16(t.v6_iv + 4 * r0 + 2));
+      if (!drop) drop = !ep6_has(t, dh, dl, ek, eh);
       out6[i] = drop ? CG_XDP_DROP : CG_XDP_PASS;
     }
   });

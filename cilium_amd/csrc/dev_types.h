@@ -2,8 +2,11 @@
 // kernels (kernels.hip).  Plain structs passed to kernels by value.
 #pragma once
 
+#include <hip/hip_vector_types.h>
+
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 #include "../../include/cilium_gpu.h"
 
@@ -12,8 +15,25 @@
 #else
 #define CG_HD
 #endif
+// The per-item walk functions the kernels and the host evaluators share
+// (l4_walk.h, lpm_walk.h, kafka_walk.h): always inlined, as in the kernels.
+#define CG_HDI CG_HD inline __attribute__((always_inline))
 
 namespace cg {
+
+// 16 bytes of a table or record in one load.  The kernels read them at
+// addresses the layouts align to 8 bytes only (&KafkaSumDev::any, a caller's
+// cg_kafka_request), which the device allows; a host build would be free to
+// use an aligned vector move there, so the host copies.
+CG_HD inline uint4 load16(const void* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return *reinterpret_cast<const uint4*>(p);
+#else
+  uint4 v;
+  memcpy(&v, p, sizeof(v));
+  return v;
+#endif
+}
 
 // ------------------------------------------------------------------ L4 ----
 // Cuckoo hash of policy keys (2 choices × 64-B buckets of 4 slots).
@@ -804,7 +824,9 @@ CG_HD inline uint64_t ipc_v4_value(const IpcacheDev& t, uint32_t a) {  // a in h
   return e;
 }
 
-CG_HD inline bool ipc_le128(uint64_t ah, uint64_t al, uint64_t bh, uint64_t bl) {
+// (ah, al) <= (bh, bl) as 128-bit numbers (the IPv6 tables of the ipcache and
+// of the prefilter)
+CG_HD inline bool le128(uint64_t ah, uint64_t al, uint64_t bh, uint64_t bl) {
   return ah < bh || (ah == bh && al <= bl);
 }
 
@@ -850,7 +872,7 @@ CG_HD inline void ipc_v6_narrow(const uint8_t* d, uint64_t hi, uint64_t lo, uint
 CG_HD inline uint32_t ipc_v6_run(const IpcacheDev& t, uint64_t hi, uint64_t lo, uint32_t L, uint32_t R) {
   while (L < R) {
     const uint32_t m = (L + R + 1) >> 1;
-    if (ipc_le128(t.runs6[4 * (size_t)m], t.runs6[4 * (size_t)m + 1], hi, lo)) L = m;
+    if (le128(t.runs6[4 * (size_t)m], t.runs6[4 * (size_t)m + 1], hi, lo)) L = m;
     else R = m - 1;
   }
   return L;

@@ -85,6 +85,13 @@ struct DevTables {
   }
 };
 
+// The pointer a host view of a table set takes for a vector (DevTables::add's
+// counterpart): the …State structs fill their …Dev through either.
+struct HostPtr {
+  template <class T>
+  const T* operator()(const std::vector<T>& v) const { return v.data(); }
+};
+
 // Page-locked host buffer (hipHostMalloc), grow-only.
 class PinnedMem {
  public:

@@ -374,45 +374,12 @@ void IpcacheState::build_tables() {
   }
 }
 
-IpcacheDev IpcacheState::host_view() const {
-  IpcacheDev v{};
-  v.l16x = l16x.data();
-  v.chunks = chunks.data();
-  v.code6 = code6.data();
-  v.ent6 = ent6.data();
-  v.crowd6 = crowd6.data();
-  v.runs6 = runs6.data();
-  v.v6_bits = v6_bits;
-  v.nruns6 = (uint32_t)(runs6.size() / 4);
-  v.ex4 = ex4.data();
-  v.ex6 = ex6.data();
-  v.ex4_mask = ex4_mask;
-  v.ex6_mask = ex6_mask;
-  v.ex4_probes = ex4_probes;
-  v.ex6_probes = ex6_probes;
-  return v;
-}
-
 void IpcacheState::rebuild(Engine& e) {
   build_tables();
   if (e.has_gpu()) {
     e.set_device();
     auto t = std::make_shared<DevTables>();
-    IpcacheDev d{};
-    d.l16x = t->add(l16x);
-    d.chunks = t->add(chunks);
-    d.code6 = t->add(code6);
-    d.ent6 = t->add(ent6);
-    d.crowd6 = t->add(crowd6);
-    d.runs6 = t->add(runs6);
-    d.v6_bits = v6_bits;
-    d.nruns6 = (uint32_t)(runs6.size() / 4);
-    d.ex4 = t->add(ex4);
-    d.ex6 = t->add(ex6);
-    d.ex4_mask = ex4_mask;
-    d.ex6_mask = ex6_mask;
-    d.ex4_probes = ex4_probes;
-    d.ex6_probes = ex6_probes;
+    const IpcacheDev d = view([&](const auto& v) { return t->add(v); });
     tab = std::move(t);  // publish (the caller holds the handle lock)
     dev = d;
   }

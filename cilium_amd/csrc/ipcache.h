@@ -31,7 +31,27 @@ struct IpcacheState {
   IpcacheDev dev{};                // view of tab; copy it together with tab
 
   void build_tables();
-  IpcacheDev host_view() const;
+  // The kernels' view (ptr as in PolicyMapState::view).
+  template <class Ptr>
+  IpcacheDev view(Ptr ptr) const {
+    IpcacheDev d{};
+    d.l16x = ptr(l16x);
+    d.chunks = ptr(chunks);
+    d.code6 = ptr(code6);
+    d.ent6 = ptr(ent6);
+    d.crowd6 = ptr(crowd6);
+    d.runs6 = ptr(runs6);
+    d.v6_bits = v6_bits;
+    d.nruns6 = (uint32_t)(runs6.size() / 4);
+    d.ex4 = ptr(ex4);
+    d.ex6 = ptr(ex6);
+    d.ex4_mask = ex4_mask;
+    d.ex6_mask = ex6_mask;
+    d.ex4_probes = ex4_probes;
+    d.ex6_probes = ex6_probes;
+    return d;
+  }
+  IpcacheDev host_view() const { return view(HostPtr{}); }
   void rebuild(Engine& e);
 };
 

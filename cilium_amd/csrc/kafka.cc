@@ -19,6 +19,7 @@
 #include <set>
 
 #include "json.h"
+#include "kafka_walk.h"
 
 namespace cg {
 
@@ -113,32 +114,6 @@ RuleSpec sanitize(const Json& r) {
   return s;
 }
 
-// isTopicAPIKey, pkg/kafka/policy.go:27-52
-inline bool is_topic_api_key(int k) {
-  switch (k) {
-    case 0: case 1: case 2: case 3: case 4: case 5: case 6: case 8: case 9:
-    case 19: case 20: case 21: case 23: case 24: case 27: case 28: case 34: case 35: case 37:
-      return true;
-  }
-  return false;
-}
-
-inline bool rule_matches(const KafkaRuleDev& r, const cg_kafka_request& q) {
-  // ruleMatches, pkg/kafka/policy.go:144-195
-  const bool has_topic = r.flags & kKfHasTopic;
-  if (!(r.flags & kKfKeyWild)) {
-    if (q.api_key < 0 || q.api_key >= 64 || !((r.keys >> q.api_key) & 1)) return false;
-  }
-  if (!(r.flags & kKfVerWild) && r.version != q.api_version) return false;
-  bool has_client = r.flags & kKfHasClient;
-  if (!has_topic && !has_client) return true;
-  switch (q.kind) {
-    case CG_KAFKA_K_TYPED: return !has_client || r.client_id == q.client_id;
-    case CG_KAFKA_K_CONSUMER_METADATA: return true;
-    default: return !(has_topic && is_topic_api_key(q.api_key));  // matchNonTopicRequests
-  }
-}
-
 uint32_t intern(std::unordered_map<std::string, uint32_t>& m, const std::string& s) {
   auto it = m.find(s);
   if (it != m.end()) return it->second;
@@ -164,7 +139,7 @@ void fold_rule(KafkaSumDev* sums, uint32_t sum_base, std::vector<std::vector<Kaf
       bool match = true, needs_client = false;
       if (has_topic || has_client) {
         if (c == 0) needs_client = has_client;
-        else if (c == 2) match = !(has_topic && b < 64 && is_topic_api_key((int)b));
+        else if (c == 2) match = !(has_topic && b < 64 && kf_is_topic_key((int)b));
       }
       if (!match) continue;
       if (needs_client) {
@@ -372,67 +347,30 @@ std::shared_ptr<KafkaSnapshot> kafka_compile(const char* json, size_t len) {
   return snap;
 }
 
-// Mirrors kafka_kernel (kernels.hip) step for step, so the compiler can be
-// checked against the oracle without a GPU.
+// One request through kafka_kernel's own functions (kafka_walk.h) over
+// host_view(), loaded phase by phase as the kernel loads it, so the tables and
+// the walk are checked against the oracle without a GPU.  Checked first, on
+// the host only: a redirect the snapshot has (the kernel's `known`) and a
+// topic list inside the arena.
 uint8_t kafka_eval_host(const KafkaSnapshot& s, const cg_kafka_request& q, const uint32_t* arena,
                         size_t arena_len) {
-  if (q.policy >= s.dflt_group.size()) return 0;
-  uint32_t g = s.dflt_group[q.policy];
-  if (q.remote != 0) {
-    uint64_t key = ((uint64_t)q.policy << 32) | q.remote;
-    uint32_t h = kf_hash(key) & s.ghash_mask;
-    while (s.ghash[h].key != ~0ULL) {
-      if (s.ghash[h].key == key) {
-        g = s.ghash[h].group;
-        break;
-      }
-      h = (h + 1) & s.ghash_mask;
-    }
-  }
-  const uint32_t nt = q.n_topics;
-  const uint32_t b = (q.api_key >= 0 && q.api_key < 64) ? (uint32_t)q.api_key : 64;
-  const uint32_t si = g * kKfSumsPerGroup + (nt == 0 ? kKfBuckets : 0) + b;
-  const KafkaSumDev& su = s.sums[si];
-  const int c = q.kind == CG_KAFKA_K_TYPED ? 0 : q.kind == CG_KAFKA_K_CONSUMER_METADATA ? 1 : 2;
-  const bool vin = q.api_version >= 0 && q.api_version < 64;
-  if ((su.any >> c) & 1) return 1;
-  if (vin && ((su.vm[c] >> q.api_version) & 1)) return 1;
-  if (c == 0 && (su.any & kKfSumHasClients)) {
-    const uint64_t key = ((uint64_t)si << 32) | q.client_id;
-    uint32_t h = kf_hash(key) & s.chash_mask;
-    while (s.chash[h].key != ~0ULL) {
-      if (s.chash[h].key == key) {
-        if (s.chash[h].any || (vin && ((s.chash[h].vm >> q.api_version) & 1))) return 1;
-        break;
-      }
-      h = (h + 1) & s.chash_mask;
-    }
-  }
-  for (uint32_t i = 0; i < su.x_cnt; ++i)
-    if (rule_matches(s.rules[su.x_off + i], q)) return 1;
-  if (nt == 0) return 0;
-  const uint32_t* topics = q.topic_ids;
-  uint32_t ntot = nt;
-  if (nt > CG_KAFKA_MAX_TOPICS) {
-    if (nt == CG_KAFKA_TOPICS_IN_ARENA) ntot = q.topic_ids[1];
-    if ((size_t)q.topic_ids[0] + ntot > arena_len) return 0;
-    topics = arena + q.topic_ids[0];
-  }
-  for (uint32_t t = 0; t < ntot; ++t) {
-    const uint64_t key = ((uint64_t)g << 32) | topics[t];
-    uint32_t h = kf_hash(key) & s.thash_mask;
-    bool cov = false;
-    while (s.thash[h].key != ~0ULL) {
-      if (s.thash[h].key == key) {
-        for (uint32_t i = 0; i < s.thash[h].cnt && !cov; ++i)
-          cov = rule_matches(s.rules[s.thash[h].off + i], q);
-        break;
-      }
-      h = (h + 1) & s.thash_mask;
-    }
-    if (!cov) return 0;
-  }
-  return 1;
+  const KafkaDev T = s.host_view();
+  const uint4 h = load16(&q);  // the record head: {apiKey | version << 16, kind | topics << 8 | redirect << 16, identity, clientID}
+  const int key = (int16_t)(h.x & 0xFFFF), ver = (int16_t)(h.x >> 16);
+  const uint32_t kind = h.y & 0xFF, nt = (h.y >> 8) & 0xFF, red = h.y >> 16;
+  if (red >= T.nredirects) return 0;
+  if (nt > CG_KAFKA_MAX_TOPICS &&
+      (size_t)q.topic_ids[0] + (nt == CG_KAFKA_TOPICS_IN_ARENA ? q.topic_ids[1] : nt) > arena_len)
+    return 0;
+  // the group slot's first probe
+  const uint32_t hh = kf_hash(((unsigned long long)red << 32) | h.z) & T.ghash_mask;
+  const uint32_t g = kf_group(T, T.dflt_group[red], load16(T.ghash + hh), hh, h.z, red);
+  // the summary
+  const uint32_t c = kf_class(kind), si = kf_sum_index(g, nt, key);
+  const uint4 tail = load16(&T.sums[si].any);
+  if (kf_fast(tail.x, T.sums[si].vm[c], c, ver)) return 1;
+  if (!kf_needs_slow(tail, c, nt)) return 0;
+  return (uint8_t)kf_slow(T, q.topic_ids, arena, g, si, tail, key, ver, kind, c, nt, h.w);
 }
 
 void KafkaSnapshot::upload(Engine& e) {

@@ -36,6 +36,21 @@ struct KafkaSnapshot {
   KafkaDictDev ddict[2] = {};
   LaunchFence fence;  // last member: queued kernels finish before the buffers go (engine.h)
   void upload(Engine& e);
+  // `dev` over the host vectors, for the walk functions on the CPU (no counters).
+  KafkaDev host_view() const {
+    KafkaDev v{};
+    v.sums = sums.data();
+    v.rules = rules.data();
+    v.thash = thash.data();
+    v.thash_mask = thash_mask;
+    v.chash = chash.data();
+    v.chash_mask = chash_mask;
+    v.ghash = ghash.data();
+    v.ghash_mask = ghash_mask;
+    v.dflt_group = dflt_group.data();
+    v.nredirects = (uint32_t)dflt_group.size();
+    return v;
+  }
 };
 
 std::shared_ptr<KafkaSnapshot> kafka_compile(const char* json, size_t len);

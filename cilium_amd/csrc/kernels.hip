@@ -10,7 +10,10 @@
 
 #include "../../include/cilium_gpu.h"
 #include "dev_types.h"
+#include "kafka_walk.h"
 #include "kernels.h"
+#include "l4_walk.h"
+#include "lpm_walk.h"
 
 namespace cg {
 
@@ -23,143 +26,8 @@ __device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_bswap
 __device__ __forceinline__ uint64_t bswap64(uint64_t x) { return __builtin_bswap64(x); }
 
 // =============================================================== L4 ======
-// __policy_can_access (bpf/lib/policy.h:46-110) per tuple.
-
-// Verdict for one tuple given which lookup hit (1: L4, 2: L3, 3: wildcard
-// identity L4, 0: none) and the slot value {entry id, proxy_port_be << 16}.
-__device__ __forceinline__ int32_t l4_verdict(int which, uint32_t val, uint32_t flags) {
-  if (which == 1 || which == 3) return (int32_t)(val >> 16);  // return policy->proxy_port
-  if (which == 2) return 0;  // TC_ACT_OK: the L3 entry's proxy_port is ignored
-  if (flags & CG_L4_F_CB_POLICY) return 0;
-  return (flags & CG_L4_F_FRAGMENT) ? CG_DROP_FRAG_NOSUPPORT : CG_DROP_POLICY;
-}
-
-// The verdict wrappers (bpf/lib/policy.h:126-163).  mode & 3:
-// CG_L4_CAN_ACCESS = __policy_can_access with the tuple's own direction and
-// fragment flags; CG_L4_INGRESS = policy_can_access_ingress (dir CT_INGRESS,
-// the tuple's is_fragment); CG_L4_EGRESS = policy_can_egress (dir CT_EGRESS,
-// is_fragment false).  Both wrappers return DROP_POLICY for any negative
-// result, or TC_ACT_OK when built with IGNORE_DROP (mode & CG_L4_IGNORE_DROP).
-__device__ __forceinline__ uint32_t l4_mode_word(uint32_t w1, uint32_t mode) {
-  const uint32_t m = mode & 3u;
-  if (m == CG_L4_INGRESS) return w1 | (CG_L4_F_INGRESS << 24);
-  if (m == CG_L4_EGRESS) return w1 & ~((CG_L4_F_INGRESS | CG_L4_F_FRAGMENT) << 24);
-  return w1;
-}
-__device__ __forceinline__ int32_t l4_wrap(int32_t v, uint32_t mode) {
-  if ((mode & 3u) != CG_L4_CAN_ACCESS && v < 0) return (mode & CG_L4_IGNORE_DROP) ? 0 : CG_DROP_POLICY;
-  return v;
-}
-
-// The three policy_key lookups of __policy_can_access (bpf/lib/policy.h:61-109)
-// in priority order: j=0 {id, dport, proto, dir} (skipped for fragments),
-// j=1 {id, 0, 0, dir}, j=2 {0, dport, proto, dir} (skipped for fragments).
-// The keys share their hash products: h_j = fin(lo_j*M1 + hi_j*M2) with
-// lo in {id, id, 0} and hi in {pp, eg, pp}.
-//
-// Candidates come from the fingerprint words: a zero-byte test on word^fp
-// (it can flag a byte next to a true match as well, which only costs a slot
-// read); bit p = slot*8 + j*2 + c for key j, bucket choice c.  A policy key
-// sits in one slot, so the lowest j whose slot key matches is the verdict;
-// candidates are walked in bit order and a j=0 match ends the walk.
-struct L4Cand {
-  uint64_t cand;   // candidate bits (slot*8 + j*2 + c)
-  uint32_t bk[6];  // bucket of (key j, choice c) at index j*2+c
-  uint32_t w0, pp, eg;
-};
-
-template <typename FpWord>
-__device__ __forceinline__ L4Cand l4_candidates(const L4Dev& t, FpWord fpw, uint32_t w0, uint32_t w1, bool frag) {
-  L4Cand r;
-  const uint32_t flags = w1 >> 24;
-  // key.egress = !dir with dir = CT_INGRESS(1) / CT_EGRESS(0)
-  r.eg = (flags & CG_L4_F_INGRESS) ? 0u : (1u << 24);
-  r.pp = (w1 & 0xFFFFFF) | r.eg;  // dport | proto << 16 | egress << 24
-  r.w0 = w0;
-  const uint32_t P = w0 * kL4MulLo, Q = r.pp * kL4MulHi, E = r.eg * kL4MulHi;
-  const uint32_t h[3] = {l4_fin(P + Q), l4_fin(P + E), l4_fin(Q)};
-  r.cand = 0;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    uint32_t fp;
-    l4_place_h(h[j], t.bucket_mask, &r.bk[2 * j], &r.bk[2 * j + 1], &fp);
-    if (j != 1 && frag) continue;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const uint32_t x = fpw(r.bk[2 * j + c]) ^ (fp * 0x01010101u);
-      const uint32_t z = (x - 0x01010101u) & ~x & 0x80808080u;  // bit 8s+7: byte s zero
-      r.cand |= (uint64_t)(z >> 7) << (j * 2 + c);
-    }
-  }
-  return r;
-}
-
-// The slot a candidate bit names (selects, not indexing: a dynamically
-// indexed array would live in scratch).
-__device__ __forceinline__ const uint4* l4_slot(const L4Dev& t, const L4Cand& r, int bit) {
-  const uint32_t jc = bit & 7;
-  // masks, not a select chain: the compiler turns that into a scratch array
-  const uint32_t b = (r.bk[0] & (0u - (jc == 0))) | (r.bk[1] & (0u - (jc == 1))) | (r.bk[2] & (0u - (jc == 2))) |
-                     (r.bk[3] & (0u - (jc == 3))) | (r.bk[4] & (0u - (jc == 4))) | (r.bk[5] & (0u - (jc >= 5)));
-  return reinterpret_cast<const uint4*>(t.slots + (size_t)b * 4 + (bit >> 3));
-}
-
-__device__ __forceinline__ bool l4_key_is(const L4Cand& r, int j, const uint4& v) {
-  const uint32_t klo = j == 2 ? 0u : r.w0;
-  const uint32_t khi = j == 1 ? r.eg : r.pp;
-  return v.x == klo && v.y == khi;
-}
-
-// Candidates walked in bit order; a key sits in one slot, so the lowest j
-// whose slot matches is the verdict, and a j=0 match ends the walk.  The
-// first candidate's slot arrives loaded (v0, issued together with the other
-// tuples' first loads); later ones load here (false fingerprint matches and
-// tuples that need more than one key are the minority).
-__device__ __forceinline__ int l4_walk(const L4Dev& t, const L4Cand& r, const uint4& v0, uint32_t* val) {
-  uint64_t cand = r.cand;
-  if (!cand) return 0;
-  int best = 0;
-  {
-    const int bit = __builtin_ctzll(cand);
-    cand &= cand - 1;
-    const int j = (bit & 7) >> 1;
-    if (l4_key_is(r, j, v0)) {
-      *val = v0.z;
-      best = j + 1;
-      if (j == 0) return best;
-    }
-  }
-  while (cand) {
-    const int bit = __builtin_ctzll(cand);
-    cand &= cand - 1;
-    const int j = (bit & 7) >> 1;
-    if (best && j + 1 >= best) continue;
-    const uint4 v = *l4_slot(t, r, bit);
-    if (l4_key_is(r, j, v)) {
-      *val = v.z;
-      best = j + 1;
-      if (j == 0) break;
-    }
-  }
-  return best;
-}
-
-// The three policy_key lookups of __policy_can_access (bpf/lib/policy.h:61-109)
-// in priority order: j=0 {id, dport, proto, dir} (skipped for fragments),
-// j=1 {id, 0, 0, dir}, j=2 {0, dport, proto, dir} (skipped for fragments).
-// The keys share their hash products: h_j = fin(lo_j*M1 + hi_j*M2) with
-// lo in {id, id, 0} and hi in {pp, eg, pp}.
-//
-// Candidates come from the fingerprint words: a zero-byte test on word^fp
-// (it can flag a byte next to a true match as well, which only costs a slot
-// read); bit p = slot*8 + j*2 + c for key j, bucket choice c.
-template <typename FpWord>
-__device__ __forceinline__ int l4_resolve(const L4Dev& t, FpWord fpw, uint32_t w0, uint32_t w1, bool frag,
-                                          uint32_t* val) {
-  const L4Cand r = l4_candidates(t, fpw, w0, w1, frag);
-  const uint4 v0 = r.cand ? *l4_slot(t, r, __builtin_ctzll(r.cand)) : make_uint4(0, 0, 0, 0);
-  return l4_walk(t, r, v0, val);
-}
+// __policy_can_access (bpf/lib/policy.h:46-110) per tuple: the lookups and
+// the verdict are l4_walk.h; here the loads, the counters and the kernels.
 
 // Counter entry in LDS: one u64 per entry id, packets in bits 40..63, bytes in
 // bits 0..39 (lengths below 64 KiB; longer ones go straight to the global
@@ -198,7 +66,7 @@ __device__ __forceinline__ uint32_t ipc_v6_identity(const IpcacheDev& ipc, uint6
                                                     uint4 kr, uint32_t v) {
   uint64_t xv;
   if (en.w && ipc_ex6_find(ipc, hi, lo, ipc_ex6_hash(hi, lo) & ipc.ex6_mask, &xv)) return (uint32_t)xv;  // a /128
-  if (!ipc_le128(((uint64_t)kr.y << 32) | kr.x, ((uint64_t)kr.w << 32) | kr.z, hi, lo))
+  if (!le128(((uint64_t)kr.y << 32) | kr.x, ((uint64_t)kr.w << 32) | kr.z, hi, lo))
     v = (uint32_t)ipc_v6_search_value(ipc, hi, lo, en.x, en.y, en.z);
   return v;
 }
@@ -309,7 +177,7 @@ __global__ __launch_bounds__(1024) void l4_fp_kernel(L4Dev t, IpcacheDev ipc, co
                             (w[u][1] >> 24) & CG_L4_F_FRAGMENT);
 #pragma unroll
     for (uint32_t u = 0; u < kL4Tuples; ++u)  // a lane with no candidate re-reads bucket 0's first slot
-      v0[u] = *l4_slot(t, rc[u], rc[u].cand ? __builtin_ctzll(rc[u].cand) : 0);
+      v0[u] = l4_slot(t, rc[u], rc[u].cand ? __builtin_ctzll(rc[u].cand) : 0);
 #pragma unroll
     for (uint32_t u = 0; u < kL4Tuples; ++u) {
       const size_t i = base + u * blockDim.x + threadIdx.x;
@@ -375,74 +243,6 @@ __global__ __launch_bounds__(256) void l4_kernel(L4Dev t, IpcacheDev ipc, const 
 // check_v4 / check_v6 (bpf/bpf_xdp.c:97-156): drop when the source is covered
 // by the CIDR maps, else pass iff the destination is a local endpoint.
 
-__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
-
-// Endpoint probes continue past the first slot (the first one is issued by
-// the caller together with the other requests' loads).
-__device__ __forceinline__ bool ep4_probe_more(const LpmDev& t, uint32_t a, uint32_t h) {
-  for (uint32_t probe = 1; probe <= t.ep4_mask; ++probe) {
-    h = (h + 1) & t.ep4_mask;
-    const uint32_t k = t.ep4_keys[h];
-    if (k == a) return true;
-    if (k == 0) return false;
-  }
-  return false;
-}
-
-__device__ __forceinline__ bool ep6_probe_more(const LpmDev& t, uint64_t hi, uint64_t lo, uint32_t h) {
-  for (uint32_t probe = 1; probe <= t.ep6_mask; ++probe) {
-    h = (h + 1) & t.ep6_mask;
-    const uint4 k = *reinterpret_cast<const uint4*>(t.ep6_keys + 2 * (size_t)h);
-    if (u64_of(k.x, k.y) == hi && u64_of(k.z, k.w) == lo) return true;
-    if ((k.x | k.y | k.z | k.w) == 0) return false;
-  }
-  return false;
-}
-
-// A mixed /16: its /24 code, then for a partial /24 the leaf by rank.
-__device__ __forceinline__ bool v4_mixed(const LpmDev& t, uint32_t s, uint32_t tw) {
-  const uint32_t q = s >> 16;
-  const uint32_t m = t.top_rank[q >> 4] + __popc(lpm_partials(tw) & ((1u << (2 * (q & 15))) - 1));
-  const uint32_t k = (s >> 8) & 255;
-  const uint4* chunk = reinterpret_cast<const uint4*>(t.mid + (size_t)m * 16);
-  const uint4 cw = chunk[k >> 6];
-  const uint32_t wi = (k >> 4) & 3;
-  const uint32_t w = wi == 0 ? cw.x : wi == 1 ? cw.y : wi == 2 ? cw.z : cw.w;
-  const uint32_t c = (w >> (2 * (k & 15))) & 3;
-  if (c != kLpmPartial) return c == 1;
-  uint32_t rank = t.leaf_base[m];
-  for (uint32_t j = 0; j < (k >> 6); ++j) {
-    const uint4 x = chunk[j];
-    rank += __popc(lpm_partials(x.x)) + __popc(lpm_partials(x.y)) + __popc(lpm_partials(x.z)) +
-            __popc(lpm_partials(x.w));
-  }
-  rank += (wi > 0 ? __popc(lpm_partials(cw.x)) : 0) + (wi > 1 ? __popc(lpm_partials(cw.y)) : 0) +
-          (wi > 2 ? __popc(lpm_partials(cw.z)) : 0);
-  rank += __popc(lpm_partials(w) & ((1u << (2 * (k & 15))) - 1));
-  return (t.leaves[(size_t)rank * 4 + ((s & 0xFF) >> 6)] >> (s & 63)) & 1;
-}
-
-__device__ __forceinline__ bool le128(uint64_t ah, uint64_t al, uint64_t bh, uint64_t bl) {
-  return ah < bh || (ah == bh && al <= bl);
-}
-
-// Binary search over intervals [L, R] for the last lo <= addr (more than two
-// candidates in a mixed bucket: rare with ~2 buckets per interval).
-__device__ __forceinline__ int64_t v6_search(const LpmDev& t, uint64_t hi, uint64_t lo, int64_t L, int64_t R) {
-  int64_t ans = -1;
-  while (L <= R) {
-    const int64_t m = (L + R) >> 1;
-    const uint4 x = *reinterpret_cast<const uint4*>(t.v6_iv + 4 * m);
-    if (le128(u64_of(x.x, x.y), u64_of(x.z, x.w), hi, lo)) {
-      ans = m;
-      L = m + 1;
-    } else {
-      R = m - 1;
-    }
-  }
-  return ans;
-}
-
 constexpr uint32_t kLpmV4 = 8, kLpmV6 = 2;  // addresses per lane per iteration
 
 __global__ __launch_bounds__(256) void lpm_kernel(LpmDev t, bool v4f, bool v6f, const uint2* __restrict__ v4,
@@ -451,7 +251,6 @@ __global__ __launch_bounds__(256) void lpm_kernel(LpmDev t, bool v4f, bool v6f, 
                                                   uint8_t* __restrict__ out6) {
   uint32_t drops = 0, passes = 0;
   const size_t nthreads = (size_t)gridDim.x * blockDim.x;
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   // ---- IPv4: {saddr, daddr} per packet
   for (size_t base = (size_t)blockIdx.x * blockDim.x * kLpmV4; base < n4; base += nthreads * kLpmV4) {
     uint2 r[kLpmV4];
@@ -475,19 +274,8 @@ __global__ __launch_bounds__(256) void lpm_kernel(LpmDev t, bool v4f, bool v6f, 
     for (uint32_t u = 0; u < kLpmV4; ++u) {
       const size_t i = base + u * blockDim.x + threadIdx.x;
       if (i >= n4) continue;
-      const uint32_t s = bswap32(r[u].x);
-      const uint32_t c = (w[u] >> (2 * ((s >> 16) & 15))) & 3;
-      bool drop = c == 1;
-      if (c == kLpmPartial) drop = v4_mixed(t, s, w[u]);
-      if (!drop) {
-        const uint32_t a = r[u].y;
-        bool has;
-        if (a == 0) has = t.ep4_zero;
-        else if (ek[u] == a) has = true;
-        else if (ek[u] == 0) has = false;
-        else has = ep4_probe_more(t, a, eh[u]);
-        drop = !has;
-      }
+      bool drop = v4_covered(t, bswap32(r[u].x), w[u]);
+      if (!drop) drop = !ep4_has(t, r[u].y, ek[u], eh[u]);
       const uint8_t v = drop ? CG_XDP_DROP : CG_XDP_PASS;
       __builtin_nontemporal_store(v, out4 + i);
       drops += drop;
@@ -527,15 +315,13 @@ __global__ __launch_bounds__(256) void lpm_kernel(LpmDev t, bool v4f, bool v6f, 
       mx[u] = t.v6_mix[code[u] == kLpmPartial ? m : 0];
     }
     // the top two candidates of a mixed bucket, loaded together
-    int64_t L[kLpmV6], R[kLpmV6];
+    V6Window win[kLpmV6];
     uint4 c1lo[kLpmV6], c1hi[kLpmV6], c0lo[kLpmV6], c0hi[kLpmV6];
 #pragma unroll
     for (uint32_t u = 0; u < kLpmV6; ++u) {
       const bool mixed = code[u] == kLpmPartial;
-      const uint32_t span = mx[u] & 15;
-      R[u] = mixed ? (int64_t)(mx[u] >> 4) : -1;
-      L[u] = span == 15 ? 0 : R[u] - span;
-      const int64_t r1 = mixed ? R[u] : 0, r0 = mixed && R[u] - 1 >= L[u] ? R[u] - 1 : r1;
+      win[u] = v6_window(mx[u], mixed);
+      const int64_t r1 = mixed ? win[u].R : 0, r0 = mixed && win[u].R - 1 >= win[u].L ? win[u].R - 1 : r1;
       const uint4* p1 = reinterpret_cast<const uint4*>(t.v6_iv + 4 * r1);
       const uint4* p0 = reinterpret_cast<const uint4*>(t.v6_iv + 4 * r0);
       c1lo[u] = p1[0];
@@ -548,45 +334,14 @@ __global__ __launch_bounds__(256) void lpm_kernel(LpmDev t, bool v4f, bool v6f, 
       const size_t j = base + u * blockDim.x + threadIdx.x;
       if (j >= n6) continue;
       bool drop = code[u] == 1;
-      if (code[u] == kLpmPartial) {
-        uint64_t eh_ = 0, el_ = 0;
-        bool found = false;
-        if (le128(u64_of(c1lo[u].x, c1lo[u].y), u64_of(c1lo[u].z, c1lo[u].w), sh[u], sl[u])) {
-          eh_ = u64_of(c1hi[u].x, c1hi[u].y);
-          el_ = u64_of(c1hi[u].z, c1hi[u].w);
-          found = true;
-        } else if (R[u] - 1 >= L[u]) {
-          if (le128(u64_of(c0lo[u].x, c0lo[u].y), u64_of(c0lo[u].z, c0lo[u].w), sh[u], sl[u])) {
-            eh_ = u64_of(c0hi[u].x, c0hi[u].y);
-            el_ = u64_of(c0hi[u].z, c0hi[u].w);
-            found = true;
-          } else if (R[u] - 2 >= L[u]) {
-            const int64_t ans = v6_search(t, sh[u], sl[u], L[u], R[u] - 2);
-            if (ans >= 0) {
-              const uint4 x = reinterpret_cast<const uint4*>(t.v6_iv + 4 * ans)[1];
-              eh_ = u64_of(x.x, x.y);
-              el_ = u64_of(x.z, x.w);
-              found = true;
-            }
-          }
-        }
-        drop = found && le128(sh[u], sl[u], eh_, el_);
-      }
-      if (!drop) {
-        bool has;
-        if ((dh[u] | dl[u]) == 0) has = t.ep6_zero;
-        else if (u64_of(e[u].x, e[u].y) == dh[u] && u64_of(e[u].z, e[u].w) == dl[u]) has = true;
-        else if ((e[u].x | e[u].y | e[u].z | e[u].w) == 0) has = false;
-        else has = ep6_probe_more(t, dh[u], dl[u], eh[u]);
-        drop = !has;
-      }
+      if (code[u] == kLpmPartial) drop = v6_covered(t, sh[u], sl[u], win[u], c1lo[u], c1hi[u], c0lo[u], c0hi[u]);
+      if (!drop) drop = !ep6_has(t, dh[u], dl[u], e[u], eh[u]);
       const uint8_t v = drop ? CG_XDP_DROP : CG_XDP_PASS;
       __builtin_nontemporal_store(v, out6 + j);
       drops += drop;
       passes += !drop;
     }
   }
-  (void)tid;
   // wave reduce then one atomic per wave
   for (int o = 32; o > 0; o >>= 1) {
     drops += __shfl_down(drops, o, kWave);
@@ -602,80 +357,10 @@ __global__ __launch_bounds__(256) void lpm_kernel(LpmDev t, bool v4f, bool v6f, 
 // kafkaRedirect.canAccess → RequestMessage.MatchesRule
 // (pkg/proxy/kafka.go:117-153, pkg/kafka/policy.go:144-225).
 
-__device__ __forceinline__ bool kf_is_topic_key(int k) {
-  // isTopicAPIKey (pkg/kafka/policy.go:27-52) as a bitmask over 0..37
-  const unsigned long long m = (1ULL << 0) | (1ULL << 1) | (1ULL << 2) | (1ULL << 3) | (1ULL << 4) |
-                               (1ULL << 5) | (1ULL << 6) | (1ULL << 8) | (1ULL << 9) | (1ULL << 19) |
-                               (1ULL << 20) | (1ULL << 21) | (1ULL << 23) | (1ULL << 24) | (1ULL << 27) |
-                               (1ULL << 28) | (1ULL << 34) | (1ULL << 35) | (1ULL << 37);
-  return k >= 0 && k < 64 && ((m >> k) & 1);
-}
-
-__device__ __forceinline__ bool kf_rule_matches(const KafkaRuleDev& r, int key, int ver, uint32_t kind,
-                                                uint32_t client) {
-  if (!(r.flags & kKfKeyWild)) {
-    if (key < 0 || key >= 64 || !((r.keys >> key) & 1)) return false;
-  }
-  if (!(r.flags & kKfVerWild) && r.version != ver) return false;
-  const bool has_client = r.flags & kKfHasClient;
-  const bool has_topic = r.flags & kKfHasTopic;
-  if (!has_topic && !has_client) return true;
-  if (kind == CG_KAFKA_K_TYPED) return !has_client || r.client_id == client;
-  if (kind == CG_KAFKA_K_CONSUMER_METADATA) return true;
-  return !(has_topic && kf_is_topic_key(key));
-}
-
 __device__ __forceinline__ void kf_flush(unsigned long long* counters, uint32_t red, uint32_t allow,
                                          uint32_t deny) {
   if (allow) atomicAdd(&counters[red * 2], (unsigned long long)allow);
   if (deny) atomicAdd(&counters[red * 2 + 1], (unsigned long long)deny);
-}
-
-// Slow part of one request: clientID table (typed requests against clientID
-// rules), exception rules, then per topic the (group, topic) rule list.
-__device__ __forceinline__ uint32_t kf_slow(const KafkaDev& T, const uint32_t* tids, const uint32_t* __restrict__ arena,
-                                         uint32_t g, uint32_t si, uint4 tail, int key, int ver, uint32_t kind,
-                                         uint32_t c, uint32_t nt, uint32_t client) {
-  const bool vin = ver >= 0 && ver < 64;
-  if (c == 0 && (tail.x & kKfSumHasClients)) {
-    const unsigned long long k = ((unsigned long long)si << 32) | client;
-    uint32_t hh = kf_hash(k) & T.chash_mask;
-    for (uint32_t probe = 0; probe <= T.chash_mask; ++probe) {
-      const KafkaClientDev* e = T.chash + hh;
-      const uint4 a = *reinterpret_cast<const uint4*>(e);
-      const unsigned long long kk = (unsigned long long)a.x | ((unsigned long long)a.y << 32);
-      if (kk == k) {
-        const unsigned long long cvm = (unsigned long long)a.z | ((unsigned long long)a.w << 32);
-        if (e->any != 0 || (vin && ((cvm >> ver) & 1))) return 1;
-        break;
-      }
-      if (kk == ~0ULL) break;
-      hh = (hh + 1) & T.chash_mask;
-    }
-  }
-  for (uint32_t j = 0; j < tail.z; ++j)
-    if (kf_rule_matches(T.rules[tail.y + j], key, ver, kind, client)) return 1;
-  if (nt == 0) return 0;
-  // topic ids re-read from the record, or its topic tail (cached)
-  const uint32_t* tsrc = nt > CG_KAFKA_MAX_TOPICS ? arena + tids[0] : tids;
-  if (nt == CG_KAFKA_TOPICS_IN_ARENA) nt = tids[1];
-  for (uint32_t t = 0; t < nt; ++t) {
-    const unsigned long long k = ((unsigned long long)g << 32) | tsrc[t];
-    uint32_t hh = kf_hash(k) & T.thash_mask;
-    bool cov = false;
-    for (uint32_t probe = 0; probe <= T.thash_mask; ++probe) {
-      const KafkaTopicDev e = T.thash[hh];
-      if (e.key == k) {
-        for (uint32_t j = 0; j < e.cnt && !cov; ++j)
-          cov = kf_rule_matches(T.rules[e.off + j], key, ver, kind, client);
-        break;
-      }
-      if (e.key == ~0ULL) break;
-      hh = (hh + 1) & T.thash_mask;
-    }
-    if (!cov) return 0;
-  }
-  return 1;
 }
 
 // kKafkaReqs requests per lane per iteration, in phases so that each phase's
@@ -725,11 +410,8 @@ __device__ __forceinline__ void kf_slow_one(const KafkaDev& T, const KfLayout& L
                                             uint32_t i, uint32_t g, uint4 h, KfCount& cnt) {
   const int key = (int16_t)(h.x & 0xFFFF), ver = (int16_t)(h.x >> 16);
   const uint32_t kind = h.y & 0xFF, nt = (h.y >> 8) & 0xFF, red = h.y >> 16;
-  const uint32_t b = (key >= 0 && key < 64) ? (uint32_t)key : 64u;
-  const uint32_t c = kind == CG_KAFKA_K_TYPED ? 0 : kind == CG_KAFKA_K_CONSUMER_METADATA ? 1 : 2;
-  const uint32_t si = g * kKfSumsPerGroup + (nt == 0 ? kKfBuckets : 0) + b;
-  const uint4 tail = *reinterpret_cast<const uint4*>(&T.sums[si].any);
-  const uint32_t v = kf_slow(T, L.tids(i), arena, g, si, tail, key, ver, kind, c, nt, h.w);
+  const uint32_t si = kf_sum_index(g, nt, key);
+  const uint32_t v = kf_slow(T, L.tids(i), arena, g, si, load16(&T.sums[si].any), key, ver, kind, kf_class(kind), nt, h.w);
   out[i] = (uint8_t)v;
   cnt.add(T, red, v);
 }
@@ -768,27 +450,7 @@ __global__ __launch_bounds__(kKafkaThreads) void kafka_kernel(KafkaDev T, KfLayo
       g[u] = T.dflt_group[red < T.nredirects ? red : 0];
     }
 #pragma unroll
-    for (uint32_t u = 0; u < kKafkaReqs; ++u) {
-      if (h[u].z == 0) continue;
-      const uint32_t red = h[u].y >> 16;
-      if (e[u].x == h[u].z && e[u].y == red) {
-        g[u] = e[u].z;
-        continue;
-      }
-      if (e[u].x == ~0u && e[u].y == ~0u) continue;
-      // collision: linear probing from the next slot (a separate loop, so the
-      // first probe's registers are not turned into a pointer phi)
-      uint32_t slot = hh[u];
-      for (uint32_t probe = 1; probe <= T.ghash_mask; ++probe) {
-        slot = (slot + 1) & T.ghash_mask;
-        const uint4 x = *reinterpret_cast<const uint4*>(T.ghash + slot);
-        if (x.x == h[u].z && x.y == red) {
-          g[u] = x.z;
-          break;
-        }
-        if (x.x == ~0u && x.y == ~0u) break;
-      }
-    }
+    for (uint32_t u = 0; u < kKafkaReqs; ++u) g[u] = kf_group(T, g[u], e[u], hh[u], h[u].z, h[u].y >> 16);
     // summaries
     uint4 tail[kKafkaReqs];
     unsigned long long vm[kKafkaReqs];
@@ -796,24 +458,20 @@ __global__ __launch_bounds__(kKafkaThreads) void kafka_kernel(KafkaDev T, KfLayo
     for (uint32_t u = 0; u < kKafkaReqs; ++u) {
       const int key = (int16_t)(h[u].x & 0xFFFF);
       const uint32_t kind = h[u].y & 0xFF, nt = (h[u].y >> 8) & 0xFF;
-      const uint32_t b = (key >= 0 && key < 64) ? (uint32_t)key : 64u;
-      const uint32_t c = kind == CG_KAFKA_K_TYPED ? 0 : kind == CG_KAFKA_K_CONSUMER_METADATA ? 1 : 2;
-      const KafkaSumDev* su = T.sums + g[u] * kKfSumsPerGroup + (nt == 0 ? kKfBuckets : 0) + b;
-      tail[u] = *reinterpret_cast<const uint4*>(&su->any);
-      vm[u] = su->vm[c];
+      const KafkaSumDev* su = T.sums + kf_sum_index(g[u], nt, key);
+      tail[u] = load16(&su->any);
+      vm[u] = su->vm[kf_class(kind)];
     }
 #pragma unroll
     for (uint32_t u = 0; u < kKafkaReqs; ++u) {
       const size_t i = base + u * kKafkaThreads + threadIdx.x;
       const int ver = (int16_t)(h[u].x >> 16);
       const uint32_t kind = h[u].y & 0xFF, nt = (h[u].y >> 8) & 0xFF, red = h[u].y >> 16;
-      const uint32_t c = kind == CG_KAFKA_K_TYPED ? 0 : kind == CG_KAFKA_K_CONSUMER_METADATA ? 1 : 2;
+      const uint32_t c = kf_class(kind);
       const bool live = i < n;
       const bool known = red < T.nredirects;
-      uint32_t v = known ? (((tail[u].x >> c) & 1) | ((ver >= 0 && ver < 64) ? (uint32_t)((vm[u] >> ver) & 1) : 0u))
-                         : 0u;
-      const bool slow =
-          live && known && !v && ((c == 0 && (tail[u].x & kKfSumHasClients)) || tail[u].z != 0 || nt != 0);
+      uint32_t v = known ? kf_fast(tail[u].x, vm[u], c, ver) : 0u;
+      const bool slow = live && known && !v && kf_needs_slow(tail[u], c, nt);
       // wave-aggregated append to the block's queue
       const unsigned long long m = __ballot(slow);
       if (m) {

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kIpcThreads) void ipcache_kernel(IpcacheDev t, cons
           r = L[u] + sub[i + 1];
         }
         v = t.runs6[4 * (size_t)ipc_v6_run(t, hi[u], lo[u], l, r) + 2];
-      } else if (!ipc_le128(u64_of(kr[u].x, kr[u].y), u64_of(kr[u].z, kr[u].w), hi[u], lo[u])) {
+      } else if (!le128(u64_of(kr[u].x, kr[u].y), u64_of(kr[u].z, kr[u].w), hi[u], lo[u])) {
         v = ipc_v6_search_value(t, hi[u], lo[u], L[u], R[u], kIpcNoCrowd);
       }
       store_val(v, out6 + j);

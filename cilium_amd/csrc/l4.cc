@@ -70,13 +70,8 @@ void PolicyMapState::rebuild(Engine& e) {
       d_counters->zero();
     }
     auto t = std::make_shared<DevTables>();
-    L4Dev d{};
-    d.slots = t->add(slots);
-    d.fp = t->add(fp);
+    const L4Dev d = view([&](const auto& v) { return t->add(v); }, d_counters->as<unsigned long long>());
     t->counters = d_counters;
-    d.bucket_mask = bucket_mask;
-    d.max_entries = max_entries;
-    d.counters = d_counters->as<unsigned long long>();
     tab = std::move(t);  // publish (the caller holds the handle lock)
     dev = d;
   }

@@ -44,6 +44,19 @@ struct PolicyMapState {
   L4Dev dev{};                         // view of tab; copy it together with tab
   std::vector<uint64_t> host_counters;  // for handles without a GPU (always 0)
 
+  // The kernels' view: ptr(v) is its pointer for vector v (DevTables::add for a
+  // device copy, HostPtr for the host's own vectors, which has no counters).
+  template <class Ptr>
+  L4Dev view(Ptr ptr, unsigned long long* counters) const {
+    L4Dev d{};
+    d.slots = ptr(slots);
+    d.fp = ptr(fp);
+    d.bucket_mask = bucket_mask;
+    d.max_entries = max_entries;
+    d.counters = counters;
+    return d;
+  }
+  L4Dev host_view() const { return view(HostPtr{}, nullptr); }
   void rebuild(Engine& e);  // cuckoo build + upload (counters preserved by id)
   void read_counters(Engine& e, uint32_t id, uint64_t* pk, uint64_t* by);
   void zero_counter(Engine& e, uint32_t id);

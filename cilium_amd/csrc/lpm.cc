@@ -235,28 +235,8 @@ void PrefilterState::rebuild(Engine& e) {
       d_counters->zero();
     }
     auto t = std::make_shared<DevTables>();
-    LpmDev d{};
-    if (v4_filter) {
-      d.top = t->add(top);
-      d.top_rank = t->add(top_rank);
-      d.mid = t->add(mid);
-      d.leaf_base = t->add(leaf_base);
-      d.leaves = t->add(leaves);
-    }
-    if (v6_filter) {
-      d.v6_code = t->add(v6_code);
-      d.v6_bits = v6_bits;
-    }
-    d.v6_mix = t->add(v6_mix);
-    d.v6_iv = t->add(v6_iv);
-    d.ep4_keys = t->add(ep4_keys);
-    d.ep4_mask = (uint32_t)ep4_keys.size() - 1;
-    d.ep4_zero = ep4_zero;
-    d.ep6_keys = t->add(ep6_keys);
-    d.ep6_mask = (uint32_t)(ep6_keys.size() / 2) - 1;
-    d.ep6_zero = ep6_zero;
+    const LpmDev d = view([&](const auto& v) { return t->add(v); }, d_counters->as<unsigned long long>());
     t->counters = d_counters;
-    d.counters = d_counters->as<unsigned long long>();
     tab = std::move(t);  // publish (the caller holds the handle lock)
     dev = d;
   }

@@ -51,6 +51,32 @@ struct PrefilterState {
   LpmDev dev{};                        // view of tab; copy it together with tab
   bool v4_filter = false, v6_filter = false;
 
+  // The kernel's view (ptr as in PolicyMapState::view); a filter that is off
+  // leaves its tables null.
+  template <class Ptr>
+  LpmDev view(Ptr ptr, unsigned long long* counters) const {
+    LpmDev d{};
+    if (v4_filter) {
+      d.top = ptr(top);
+      d.top_rank = ptr(top_rank);
+      d.mid = ptr(mid);
+      d.leaf_base = ptr(leaf_base);
+      d.leaves = ptr(leaves);
+    }
+    if (v6_filter) d.v6_code = ptr(v6_code);
+    d.v6_bits = v6_bits;  // 16..22 with the filter off too: the walk shifts by 64 - v6_bits before it looks at the code
+    d.v6_mix = ptr(v6_mix);
+    d.v6_iv = ptr(v6_iv);
+    d.ep4_keys = ptr(ep4_keys);
+    d.ep4_mask = (uint32_t)ep4_keys.size() - 1;
+    d.ep4_zero = ep4_zero;
+    d.ep6_keys = ptr(ep6_keys);
+    d.ep6_mask = (uint32_t)(ep6_keys.size() / 2) - 1;
+    d.ep6_zero = ep6_zero;
+    d.counters = counters;
+    return d;
+  }
+  LpmDev host_view() const { return view(HostPtr{}, nullptr); }
   void rebuild(Engine& e);
 };
 

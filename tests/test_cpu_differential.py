@@ -379,6 +379,21 @@ def test_l4_table_builder(host):
     assert np.array_equal(pm.eval_host_diag(t), oracle.l4(keys, ports, t)[0])
 
 
+def test_l4_branch_table_host(host):
+    """Each branch of __policy_can_access through the host evaluator, which
+    runs the L4 kernels' own lookup and verdict functions: the table of
+    test_gpu_parity.py::test_l4_branch_table, before and after the updates."""
+    from test_gpu_parity import (L4_BRANCH_EXPECT, L4_BRANCH_EXPECT_FLUSHED, L4_BRANCH_EXPECT_NO_L3,
+                                 l4_branch_table)
+    pm, t = l4_branch_table(host)
+    assert pm.eval_host_diag(t).tolist() == L4_BRANCH_EXPECT
+    pm.delete(100, 0, 0, 0)  # the L3 entry: the fallback now drops
+    assert pm.eval_host_diag(t[1:2]).tolist() == L4_BRANCH_EXPECT_NO_L3
+    pm.flush()
+    assert pm.dump_to_slice() == []
+    assert pm.eval_host_diag(t).tolist() == L4_BRANCH_EXPECT_FLUSHED
+
+
 @pytest.mark.parametrize("cfg", [(True, True), (False, False), (True, False)])
 def test_prefilter_table_builder(host, cfg):
     dyn4, dyn6 = cfg

@@ -37,29 +37,48 @@ def test_l4_config2_table_parity(gpu):
     assert (exp > 0).any() and (exp == 0).any() and (exp == -133).any() and (exp == -157).any()
 
 
+# Each branch of __policy_can_access (policy.h:61-109): a map's entries, nine
+# tuples and their verdicts — with the map as filled, for row 1 once the L3
+# entry is deleted, and with the map flushed.  The host evaluator's test
+# (test_cpu_differential.py) runs the same table.
+L4_BRANCH_ENTRIES = [
+    (100, 80, 6, 0, 10001),           # L4 ingress, proxied
+    (100, 0, 0, 0, 7777),             # L3 ingress: proxy port ignored
+    (0, 53, 17, 1, 0),                # any identity, egress UDP/53
+    (200, 443, 6, 1, 0),              # L4 egress, not proxied
+]
+L4_BRANCH_ROWS = [
+    (100, htons(80), 6, 1, 100),      # L4 hit → proxy_port as stored (be16)
+    (100, htons(81), 6, 1, 100),      # L3 fallback → 0
+    (100, htons(80), 6, 1 | 2, 100),  # fragment skips L4 → L3 hit → 0
+    (101, htons(53), 17, 0, 60),      # egress any-identity → 0
+    (101, htons(53), 17, 1, 60),      # ingress: no entry → DROP_POLICY
+    (101, htons(53), 17, 2, 60),      # egress fragment → DROP_FRAG_NOSUPPORT
+    (101, htons(54), 17, 4, 60),      # cb_policy → allow
+    (200, htons(443), 6, 0, 1500),    # egress L4 hit
+    (200, htons(443), 6, 1, 1500),    # ingress miss → drop
+]
+L4_BRANCH_EXPECT = [htons(10001), 0, 0, 0, -133, -157, 0, 0, -133]
+L4_BRANCH_EXPECT_NO_L3 = [-133]  # row 1
+L4_BRANCH_EXPECT_FLUSHED = [-133, -133, -157, -133, -133, -157, 0, -133, -133]
+
+
+def l4_branch_table(cl):
+    """The branch table's map on handle cl, and its tuples."""
+    pm = cl.policy_map()
+    for e in L4_BRANCH_ENTRIES:
+        pm.allow(*e)
+    t = np.zeros(len(L4_BRANCH_ROWS), L4_TUPLE_DTYPE)
+    for i, r in enumerate(L4_BRANCH_ROWS):
+        t[i] = r
+    return pm, t
+
+
 def test_l4_branch_table(gpu):
     """Each branch of __policy_can_access (policy.h:61-109)."""
-    pm = gpu.policy_map()
-    pm.allow(100, 80, 6, 0, 10001)        # L4 ingress, proxied
-    pm.allow(100, 0, 0, 0, 7777)          # L3 ingress: proxy port ignored
-    pm.allow(0, 53, 17, 1, 0)             # any identity, egress UDP/53
-    pm.allow(200, 443, 6, 1, 0)           # L4 egress, not proxied
-    t = np.zeros(9, L4_TUPLE_DTYPE)
-    rows = [
-        (100, htons(80), 6, 1, 100),      # L4 hit → proxy_port as stored (be16)
-        (100, htons(81), 6, 1, 100),      # L3 fallback → 0
-        (100, htons(80), 6, 1 | 2, 100),  # fragment skips L4 → L3 hit → 0
-        (101, htons(53), 17, 0, 60),      # egress any-identity → 0
-        (101, htons(53), 17, 1, 60),      # ingress: no entry → DROP_POLICY
-        (101, htons(53), 17, 2, 60),      # egress fragment → DROP_FRAG_NOSUPPORT
-        (101, htons(54), 17, 4, 60),      # cb_policy → allow
-        (200, htons(443), 6, 0, 1500),    # egress L4 hit
-        (200, htons(443), 6, 1, 1500),    # ingress miss → drop
-    ]
-    for i, r in enumerate(rows):
-        t[i] = r
+    pm, t = l4_branch_table(gpu)
     got = pm.verdicts(t)
-    assert got.tolist() == [htons(10001), 0, 0, 0, -133, -157, 0, 0, -133]
+    assert got.tolist() == L4_BRANCH_EXPECT
     keys = np.zeros(4, dtype=[("sec_label", "<u4"), ("dport", "<u2"), ("protocol", "u1"), ("egress", "u1")])
     e = pm.lookup(PolicyKey(100, 0, 0, 0))
     assert e.Packets == 2 and e.Bytes == 200
@@ -68,10 +87,10 @@ def test_l4_branch_table(gpu):
     # update path: delete the L3 entry → the fallback now drops
     pm.delete(100, 0, 0, 0)
     got = pm.verdicts(t[1:2])
-    assert got.tolist() == [-133]
+    assert got.tolist() == L4_BRANCH_EXPECT_NO_L3
     pm.flush()
     assert pm.dump_to_slice() == []
-    assert pm.verdicts(t).tolist() == [-133, -133, -157, -133, -133, -157, 0, -133, -133]
+    assert pm.verdicts(t).tolist() == L4_BRANCH_EXPECT_FLUSHED
     del keys
 
 
