@@ -2228,7 +2228,7 @@ int cg_diag_http_rules_host(uint64_t h, const void* batch, size_t nslots, const 
     auto s = http_snap(*e);
     std::vector<uint8_t> slots(nslots);
     std::vector<uint32_t> r(nslots);
-    http_eval_host(*s, (const uint8_t*)batch, arena, arena_len, slots.data(), r.data());
+    http_eval_host(*s, (const uint8_t*)batch, nslots, arena, arena_len, slots.data(), r.data());
     for (size_t i = 0; i < nslots; ++i)
       if (order[i] < n) rule[order[i]] = r[i];
   });
@@ -2240,7 +2240,7 @@ int cg_diag_http_eval_host(uint64_t h, const void* batch, size_t nslots, const u
     auto e = get(h);
     auto s = http_snap(*e);
     std::vector<uint8_t> slots(nslots);
-    http_eval_host(*s, (const uint8_t*)batch, arena, arena_len, slots.data());
+    http_eval_host(*s, (const uint8_t*)batch, nslots, arena, arena_len, slots.data());
     for (size_t i = 0; i < nslots; ++i)
       if (order[i] < n) out[order[i]] = slots[i];
   });

@@ -73,16 +73,6 @@ bool scale_comb(CombTable* t);
 // padding) is class 0: code 0 then walks as the padding byte.
 ClsDfa zero_class_first(const ClsDfa& d);
 
-// One step: s a state (raw: base, scaled: byte offset), x the byte (raw) or
-// its code 4*class (scaled).
-inline uint32_t comb_next(const uint32_t* cells, uint32_t dead, uint32_t s, uint32_t x, bool scaled = false) {
-  const uint32_t e = scaled ? cells[(s + x) >> 2] : cells[s + x];
-  if ((e & 0xFFFF) == s) return e >> 16;
-  return s > dead ? s : dead;
-}
-
-inline uint32_t comb_label(const uint32_t* cells, uint32_t s, bool scaled = false) {
-  return (scaled ? cells[(s >> 2) - 1] : cells[s - 1]) >> 16;
-}
-
+// The step and the label read are http_walk.h's (comb_step, comb_step_cls,
+// state_label), for the kernels and the host alike.
 }  // namespace cg

@@ -469,6 +469,24 @@ CG_HD inline uint32_t hash32(uint32_t x) {
   x ^= x >> 16;
   return x;
 }
+// The program of (policy, direction, port): the exact-port entry of the
+// program hash (linear probing, 0xFFFFFFFF = an empty slot), else the
+// policy's default for the direction.  P: the tables' pointer type (the
+// snapshot's host vectors, global memory, the raw kernels' LDS copies).
+template <class P>
+CG_HDI uint32_t lookup_prog(P phk, P phv, P dflt, uint32_t phash_mask, uint32_t npolicies, uint32_t policy,
+                            bool ingress, uint32_t port) {
+  if (policy >= npolicies) return kProgDeny;
+  const uint32_t key = (policy << 17) | ((uint32_t)ingress << 16) | (port & 0xFFFF);
+  uint32_t h = hash32(key) & phash_mask;
+  for (uint32_t probe = 0; probe <= phash_mask; ++probe) {
+    const uint32_t kk = phk[h];
+    if (kk == key) return phv[h];
+    if (kk == 0xFFFFFFFFu) break;
+    h = (h + 1) & phash_mask;
+  }
+  return dflt[policy * 2 + (ingress ? 1 : 0)];
+}
 // Remote-identity table of a program (staged into LDS with it): buckets of
 // 8 u32 cells — 4 identities, then their 4 mask-row block offsets — and
 // every identity in one of its two buckets, so a lookup reads at most two

@@ -42,6 +42,7 @@
 
 #include "clsdfa.h"
 #include "comb.h"
+#include "http_walk.h"
 #include "json.h"
 #include "regex.h"
 
@@ -894,15 +895,28 @@ std::shared_ptr<HttpSnapshot> http_compile(const char* json, size_t len) {
   return snap;
 }
 
-uint32_t HttpSnapshot::lookup_prog(uint32_t policy, bool ingress, uint32_t port) const {
-  if (policy >= npolicies) return kProgDeny;
-  uint32_t key = (policy << 17) | ((uint32_t)ingress << 16) | (port & 0xFFFF);
-  uint32_t h = hash32(key) & phash_mask;
-  while (phash_keys[h] != 0xFFFFFFFFu) {
-    if (phash_keys[h] == key) return phash_vals[h];
-    h = (h + 1) & phash_mask;
-  }
-  return dflt[policy * 2 + (ingress ? 1 : 0)];
+HttpDev HttpSnapshot::view(bool device) const {
+  HttpDev d{};
+  d.progs = device ? d_progs.as<HttpProg>() : progs.data();
+  d.parts = device ? d_parts.as<HttpPart>() : parts.data();
+  d.cells = device ? d_cells.as<uint32_t>() : cells.data();
+  d.dflt = device ? d_dflt.as<uint32_t>() : dflt.data();
+  d.npolicies = npolicies;
+  d.nprogs = (uint32_t)progs.size();
+  d.nparts = (uint32_t)parts.size();
+  d.epoch = epoch;
+  // LDS per workgroup = the largest rebased program table (so 160 KiB / that
+  // many workgroups share a CU); larger programs walk from global memory
+  uint32_t max_cells = 0;
+  d.lds_cells = kMaxLdsCells;
+  for (const auto& pg : progs)
+    if (walk::prog_in_lds(d, pg, walk::prog_walked(true, pg))) max_cells = std::max(max_cells, pg.cell_count);
+  d.lds_cells = std::min((max_cells + 255) & ~255u, kMaxLdsCells);
+  for (const auto& pg : progs)
+    if (walk::prog_walked(true, pg) && !walk::prog_in_lds(d, pg, true)) d.n_global_progs++;
+  d.counters = device ? d_counters.as<unsigned long long>() : nullptr;
+  d.rule_hits = device ? d.counters + 2 * (size_t)d.nprogs + 1 : nullptr;
+  return d;
 }
 
 void HttpSnapshot::upload(Engine& e) {
@@ -915,27 +929,7 @@ void HttpSnapshot::upload(Engine& e) {
   // then one hit counter per rule (rule_info order): the all-reduce vector
   d_counters.alloc((std::max<size_t>(progs.size(), 1) * 2 + 1 + rule_info.size()) * sizeof(uint64_t));
   d_counters.zero();
-  dev.progs = d_progs.as<HttpProg>();
-  dev.parts = d_parts.as<HttpPart>();
-  dev.cells = d_cells.as<uint32_t>();
-  dev.dflt = d_dflt.as<uint32_t>();
-  dev.npolicies = npolicies;
-  dev.nprogs = (uint32_t)progs.size();
-  dev.nparts = (uint32_t)parts.size();
-  dev.epoch = epoch;
-  // LDS per workgroup = the largest rebased program table (so 160 KiB / that
-  // many workgroups share a CU); larger programs walk from global memory
-  uint32_t max_cells = 0;
-  for (const auto& pg : progs)
-    if (!(pg.flags & kProgAllowAll) && (pg.flags & kProgRebased) && pg.cell_count <= kMaxLdsCells)
-      max_cells = std::max(max_cells, pg.cell_count);
-  dev.lds_cells = std::min((max_cells + 255) & ~255u, kMaxLdsCells);
-  dev.n_global_progs = 0;
-  for (const auto& pg : progs)
-    if (!(pg.flags & kProgAllowAll) && !((pg.flags & kProgRebased) && pg.cell_count <= dev.lds_cells))
-      dev.n_global_progs++;
-  dev.counters = d_counters.as<unsigned long long>();
-  dev.rule_hits = dev.counters + 2 * (size_t)dev.nprogs + 1;
+  dev = view(true);
   http_raw_upload(*this);
 }
 

@@ -49,8 +49,15 @@ struct HttpSnapshot {
   bool raw_ok = false, lists_ok = false;
   LaunchFence fence;  // last member: queued kernels finish before the buffers go (engine.h)
 
+  // The kernels' view: over the device copies, or (http_eval_host) over the
+  // host's own vectors with the counters null.
+  HttpDev view(bool device) const;
+  HttpDev host_view() const { return view(false); }
   void upload(Engine& e);
-  uint32_t lookup_prog(uint32_t policy, bool ingress, uint32_t port) const;
+  uint32_t lookup_prog(uint32_t policy, bool ingress, uint32_t port) const {
+    return cg::lookup_prog(phash_keys.data(), phash_vals.data(), dflt.data(), phash_mask, npolicies, policy, ingress,
+                           port);
+  }
 };
 
 std::shared_ptr<HttpSnapshot> http_compile(const char* json, size_t len);
@@ -87,12 +94,13 @@ void http_pack(const HttpSnapshot& s, size_t n, const uint32_t* policy, const ui
                const uint64_t* hdr_off, void* batch, size_t batch_cap, uint32_t* order, size_t* nslots,
                uint8_t* arena, size_t arena_cap, size_t* arena_used);
 
-// Walk the snapshot's tables on the host exactly as the kernel does, for
-// every slot of a batch (diagnostics / compiler tests only; the verdict API
-// never calls this).  out has one byte per slot.
+// Walk the snapshot's tables on the host with the kernel's own functions
+// (http_walk.h), for every slot of a batch (diagnostics / compiler tests
+// only; the verdict API never calls this).  out has one byte per slot, of
+// nslots; a slot the batch does not reach is 0.
 // rule (optional, one per slot): the global index of the first rule that
 // allows the slot (the per-rule hit counter it adds to), or UINT32_MAX.
-void http_eval_host(const HttpSnapshot& s, const uint8_t* batch, const uint8_t* arena, size_t arena_len,
-                    uint8_t* out, uint32_t* rule = nullptr);
+void http_eval_host(const HttpSnapshot& s, const uint8_t* batch, size_t nslots, const uint8_t* arena,
+                    size_t arena_len, uint8_t* out, uint32_t* rule = nullptr);
 
 }  // namespace cg

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <atomic>
 #include <cstddef>
 #include <array>
@@ -25,6 +26,7 @@
 
 #include "comb.h"
 #include "http.h"
+#include "http_walk.h"
 
 namespace cg {
 
@@ -474,94 +476,94 @@ void http_pack(const HttpSnapshot& s, size_t n, const uint32_t* policy, const ui
   if (arena && used > arena_cap) fail(CG_INVALID_ARGUMENT, "overflow arena too small");
 }
 
-void http_eval_host(const HttpSnapshot& s, const uint8_t* batch, const uint8_t* arena, size_t arena_len,
-                    uint8_t* out, uint32_t* rule) {
+// Every slot as one lane of http_kernel_global takes it (kernels_http.hip
+// http_chunks, then http_tiles<1>), over host_view() and through the functions
+// the kernels run (http_walk.h).  A lane's loads are made the same way: the
+// slot's meta pair, its 16-byte units (a half last unit as 8 bytes and zeros,
+// as ld_nt_unit gives it).  Leaving a slot once its verdict is settled (not
+// counted; the dead state, which is absorbing) is loop structure: the kernel
+// walks on and gets the same.
+void http_eval_host(const HttpSnapshot& s, const uint8_t* batch, size_t nslots, const uint8_t* arena,
+                    size_t arena_len, uint8_t* out, uint32_t* rule) {
+  using namespace walk;
+  const HttpDev T = s.host_view();
   HttpBatchHeader h;
   memcpy(&h, batch, sizeof(h));
-  if (h.magic != kBatchMagic || h.epoch != s.epoch) fail(CG_INVALID_ARGUMENT, "batch packed for another snapshot");
+  // Host-only checks, in front of the walk.  A stale batch, or
+  // one of more slots than given: the kernel denies every slot and counts
+  // it; here it is the caller's error.
+  if (h.magic != kBatchMagic || h.epoch != T.epoch) fail(CG_INVALID_ARGUMENT, "batch packed for another snapshot");
+  if ((size_t)h.ntiles * CG_HTTP_TILE > nslots) fail(CG_INVALID_ARGUMENT, "batch of more slots than given");
+  // No read past the batch: its length is not an argument, so the header's
+  // total_bytes bounds the chunk table, the tile table and every tile.
   const HttpChunk* chunks = (const HttpChunk*)(batch + sizeof(h));
   const HttpTile* ttab = (const HttpTile*)(batch + h.ttab_off);
-  const uint8_t* data = batch + h.tiles_off;
-  auto unit_ptr = [&](size_t slot, uint32_t u) {
-    return data + tile_unit_at(ttab[slot / CG_HTTP_TILE], u, slot % CG_HTTP_TILE);
-  };
+  bool inside = sizeof(h) + (uint64_t)h.nchunks * sizeof(HttpChunk) <= h.total_bytes &&
+                h.ttab_off <= h.total_bytes && h.tiles_off <= h.total_bytes &&
+                (uint64_t)h.ntiles * sizeof(HttpTile) <= h.total_bytes - h.ttab_off;
+  for (uint32_t t = 0; inside && t < h.ntiles; ++t)
+    inside = ((uint64_t)ttab[t].at + tile_granules(ttab[t])) * kGranule <= h.total_bytes - h.tiles_off;
+  if (!inside) fail(CG_INVALID_ARGUMENT, "batch tables or tiles past its end");
+  // No read past the arena: the kernel's bound is the header's arena_bytes.
+  const uint64_t arena_bytes = std::min<uint64_t>(h.arena_bytes, arena_len);
+
+  // a slot no chunk reaches keeps what the verdict buffer held: 0
+  std::fill(out, out + nslots, (uint8_t)0);
+  if (rule) std::fill(rule, rule + nslots, kNoHit);
   for (uint32_t c = 0; c < h.nchunks; ++c) {
-    const uint32_t prog = chunks[c].prog;
-    for (size_t sl = (size_t)chunks[c].first_tile * CG_HTTP_TILE;
-         sl < (size_t)(chunks[c].first_tile + chunks[c].ntiles) * CG_HTTP_TILE; ++sl) {
-      uint8_t meta[CG_HTTP_META_BYTES];
-      memcpy(meta, unit_ptr(sl, 0), CG_HTTP_META_BYTES);
-      uint32_t remote;
-      memcpy(&remote, meta, 4);
-      const uint32_t off = ((uint32_t)meta[4] | ((uint32_t)meta[5] << 8) | ((uint32_t)meta[6] << 16)) * 16u;
-      const uint8_t flags = meta[7];
-      uint8_t v = 0;
-      out[sl] = 0;
-      if (rule) rule[sl] = 0xFFFFFFFFu;
-      if (flags & (CG_HTTP_F_PAD | CG_HTTP_F_MALFORMED)) continue;
-      if (prog == kProgDeny) continue;
-      if (prog == kProgAllow) {
-        out[sl] = 1;
-        continue;
-      }
-      const HttpProg& pg = s.progs[prog];
-      if (pg.flags & kProgAllowAll) {
-        out[sl] = 1;
-        continue;
-      }
-      // the bytes the kernel walks: the arena string, or the tile's units
-      // (the string and its zero padding, which cannot change the verdict)
-      std::string str;
-      if (flags & CG_HTTP_F_OVERFLOW) {
-        uint32_t len = 0;
-        if ((size_t)off + 4 > arena_len) continue;
-        memcpy(&len, arena + off, 4);
-        if ((size_t)off + 4 + len > arena_len) continue;
-        str.assign((const char*)arena + off + 4, len);
-      } else {
-        const HttpTile& tt = ttab[sl / CG_HTTP_TILE];
-        for (uint32_t u = 0; u < tile_units(tt); ++u) {
-          const bool half = u + 1 == tile_units(tt) && tile_half(tt);
-          str.append((const char*)unit_ptr(sl, u + 1), half ? 8 : 16);
-          if (half) str.append(8, '\0');
+    const HttpChunk ch = chunks[c];
+    if (!chunk_ok(ch, h.ntiles)) continue;  // malformed chunk
+    const uint32_t prog = ch.prog;
+    const bool real = prog < T.nprogs;
+    HttpProg pg{};
+    if (real) pg = T.progs[prog];
+    const bool walkp = prog_walked(real, pg);
+    // http_kernel's straight-line walker (a one-part program in LDS) reads a
+    // half last unit and at most 8 units; every other walked program goes
+    // through http_tiles, which denies a half tile unwalked
+    const bool generic = !(prog_in_lds(T, pg, walkp) && pg.part_count == 1);
+    const uint32_t* blk = T.cells + pg.cell_begin;
+    const bool rebased = pg.flags & kProgRebased;
+    const uint32_t W = pg.mask_words;
+    for (uint32_t t = ch.first_tile; t < ch.first_tile + ch.ntiles; ++t) {
+      const HttpTile tt = ttab[t];
+      const uint8_t* tile = batch + h.tiles_off + (size_t)tt.at * kGranule;
+      const bool half = tile_half(tt);
+      const uint32_t units = generic ? tile_units(tt) : std::min<uint32_t>(tile_units(tt), CG_HTTP_UNITS - 1);
+      for (uint32_t lane = 0; lane < CG_HTTP_TILE; ++lane) {
+        const size_t sl = (size_t)t * CG_HTTP_TILE + lane;
+        uint2 meta;
+        memcpy(&meta, tile + lane * CG_HTTP_META_BYTES, sizeof(meta));
+        const bool counted = slot_counted(meta.y);
+        if (!walkp) out[sl] = counted && trivial_allows(prog, real);
+        if (!walkp || !counted || (generic && half)) continue;
+        const uint32_t row = remote_row(blk, pg, meta.x);
+        // a part's walk of the slot: the first rule its end state's label allows
+        auto part_hit = [&](auto cls, const HttpPart& pt, const uint32_t* cells) {
+          constexpr bool kCls = decltype(cls)::value;
+          uint32_t st = pt.start;
+          for (uint32_t u = 0; u < units && st != pt.dead; ++u) {
+            const uint8_t* up = tile + kMetaBytes + (size_t)u * kUnitBytes;
+            uint4 unit = make_uint4(0, 0, 0, 0);
+            if (half && u + 1 == units) memcpy(&unit, up + lane * 8, 8);
+            else unit = load16(up + lane * 16);
+            for (int k = 0; k < 16; ++k) st = step<kCls>(cells, pt.dead, st, get_byte(unit, k));
+          }
+          if (slot_overflow(meta.y)) st = walk_overflow<kCls>(cells, pt.dead, pt.start, arena, arena_bytes, meta, true);
+          const uint32_t lab = state_label<kCls>(cells, st);
+          return lab != 0xFFFFu ? first_meet(blk, pt.acc_off + lab * 2 * W, row, W) : kNoHit;
+        };
+        uint32_t hit = kNoHit;
+        for (uint32_t pi = 0; pi < pg.part_count; ++pi) {
+          const HttpPart pt = T.parts[pg.part_begin + pi];
+          const uint32_t* cells = rebased ? blk : T.cells + pt.walk_off;
+          hit = std::min(hit, pt.mode == kPartClass ? part_hit(std::true_type{}, pt, cells)
+                                                    : part_hit(std::false_type{}, pt, cells));
         }
+        if (pg.flags & kProgHasAlways) hit = std::min(hit, first_meet(blk, pg.always_off, row, W));
+        out[sl] = hit != kNoHit;
+        if (rule && hit != kNoHit) rule[sl] = pg.rule_base + hit;
       }
-      const uint32_t* blk = s.cells.data() + pg.cell_begin;
-      auto bmask = [&](uint32_t o, uint32_t w) { return (uint64_t)blk[o + 2 * w] | (uint64_t)blk[o + 2 * w + 1] << 32; };
-      uint32_t roff = pg.default_remote;
-      if (pg.flags & kProgRemoteDirect) {
-        if (remote - pg.rdir_base < pg.rdir_len)
-          roff = ((const uint16_t*)(s.cells.data() + pg.cell_begin + pg.rdir_off))[remote - pg.rdir_base];
-      } else
-      for (uint32_t bk : {rtab_b1(remote, pg.rtab_nb), rtab_b2(remote, pg.rtab_nb)})
-        for (uint32_t sl = 0; sl < 4; ++sl) {
-          const uint32_t* b = blk + pg.rtab_off + kRtabBucketCells * bk;
-          if (b[sl] == remote) roff = b[4 + sl];
-        }
-      // first rule (lowest bit) the mask at block offset a shares with the row
-      uint32_t hit = 0xFFFFFFFFu;
-      auto first = [&](uint32_t a) {
-        for (uint32_t w = 0; w < pg.mask_words; ++w)
-          if (const uint64_t x = bmask(a, w) & bmask(roff, w)) return w * 64 + (uint32_t)__builtin_ctzll(x);
-        return 0xFFFFFFFFu;
-      };
-      hit = std::min(hit, first(pg.always_off));
-      for (uint32_t pi = 0; pi < pg.part_count; ++pi) {
-        const HttpPart& pt = s.parts[pg.part_begin + pi];
-        const uint32_t* cells = s.cells.data() + pt.walk_off;
-        const bool scaled = pt.mode == kPartClass;
-        uint32_t st = pt.start;
-        for (unsigned char ch : str) {
-          st = comb_next(cells, pt.dead, st, ch, scaled);
-          if (st == pt.dead) break;
-        }
-        const uint32_t lab = comb_label(cells, st, scaled);
-        if (lab == kCombNoLabel) continue;
-        hit = std::min(hit, first(pt.acc_off + lab * 2 * pg.mask_words));
-      }
-      v = hit != 0xFFFFFFFFu;
-      out[sl] = v;
-      if (rule && v) rule[sl] = pg.rule_base + hit;
     }
   }
 }

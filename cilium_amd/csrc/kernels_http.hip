@@ -40,12 +40,6 @@ constexpr uint32_t kDealRun = 4;  // consecutive chunks per workgroup turn
 // deal lets the unluckiest workgroup set the kernel's tail.
 constexpr bool kDynamicDeal = true;
 
-__device__ __forceinline__ uint32_t get_byte(const uint4& w, int k) {
-  const uint32_t word = (k < 4) ? w.x : (k < 8) ? w.y : (k < 12) ? w.z : w.w;
-  return (word >> ((k & 3) * 8)) & 0xFFu;
-}
-
-
 // Class-mode step on byte B of word w, block at LDS address 0 (the fast
 // path): four VALU.  Written out because the compiler adds the dynamic-LDS
 // base (0) as an operand and then splits the byte select from the add.
@@ -147,14 +141,6 @@ struct VOut {
   }
 };
 
-// Records longer than a slot live in the overflow arena: byte loop.
-template <bool kCls>
-__device__ __forceinline__ uint32_t walk_arena(const uint32_t* __restrict__ cells, uint32_t dead, uint32_t st,
-                                              const uint8_t* __restrict__ arena, uint32_t aoff, uint32_t len) {
-  for (uint32_t p = 0; p < len && st != dead; ++p) st = step<kCls>(cells, dead, st, arena[aoff + p]);
-  return st;
-}
-
 // A tile's meta block (8 bytes per lane: remote identity, overflow arena
 // offset / 16 | flags << 24) and its string units (unit u ≥ 1 of lane l at
 // units[(u - 1) * 64 + l]).
@@ -203,21 +189,6 @@ __device__ __forceinline__ uint4 ld_nt_unit(const TileRef& tr, uint32_t k, uint3
     return make_uint4(v.x, v.y, 0u, 0u);
   }
   return ld_nt(tr.units + k * kWave + l);
-}
-
-// The overflow string of a lane whose meta word is m (arena entry: u32 length,
-// bytes).  An entry reaching past the batch's arena (arena_bytes, from its
-// header) ends in the dead state: the request is denied.
-template <bool kCls>
-__device__ __forceinline__ uint32_t walk_overflow(const uint32_t* __restrict__ cells, uint32_t dead, uint32_t st,
-                                                 const uint8_t* __restrict__ arena, uint64_t arena_bytes, uint2 m,
-                                                 bool ov) {
-  if (!ov) return st;
-  const uint64_t aoff = (uint64_t)(m.y & 0xFFFFFFu) * 16u;
-  if (aoff + 4 > arena_bytes) return dead;
-  const uint32_t len = *reinterpret_cast<const uint32_t*>(arena + aoff);
-  if (aoff + 4 + len > arena_bytes) return dead;
-  return walk_arena<kCls>(cells, dead, st, arena, (uint32_t)aoff + 4, len);
 }
 
 // The first-match hits of a wave's 64 requests (hit = rule bit, or kNoHit),
@@ -282,8 +253,8 @@ __device__ __forceinline__ void http_tiles(const HttpDev& T, const HttpProg& pg,
     tu[j] = valid[j] && !half ? tile_units(tt) : 0u;
     units = max(units, tu[j]);
     meta[j] = tr[j].meta[lane];
-    const uint32_t flags = meta[j].y >> 24;
-    counted[j] = valid[j] && !half && !(flags & (CG_HTTP_F_PAD | CG_HTTP_F_MALFORMED));
+    const uint32_t flags = meta[j].y >> 24;  // (slot_overflow, written out: the call changed this code)
+    counted[j] = valid[j] && !half && slot_counted(meta[j].y);
     overflow[j] = counted[j] && (flags & CG_HTTP_F_OVERFLOW);
     any_overflow |= overflow[j];
     row[j] = remote_row(blk, pg, meta[j].x);
@@ -424,9 +395,8 @@ __device__ __forceinline__ void http_tile_n(const HttpDev& T, const HttpProg& pg
     unit[k] = k < kPre ? cur.u[k < kPre ? k : 0] : ld_nt_unit(tr, k, lane_now(), kHalf && k == N - 1);
   if (has_next) tile_prefetch(trn, nunits, lane, nxt);
   __builtin_amdgcn_sched_barrier(0);
-  const uint32_t flags = meta.y >> 24;
-  const bool counted = !(flags & (CG_HTTP_F_PAD | CG_HTTP_F_MALFORMED));
-  const bool overflow = counted && (flags & CG_HTTP_F_OVERFLOW);
+  const bool counted = slot_counted(meta.y);
+  const bool overflow = counted && slot_overflow(meta.y);
   const uint32_t dead = pt.dead;
   uint32_t st = pt.start;
 #pragma unroll
@@ -619,7 +589,7 @@ __device__ __forceinline__ void http_chunks(const HttpDev& T, const uint8_t* __r
   for (; cr < nchunks;) {
   for (uint32_t c = cr; c < min(nchunks, cr + kDealRun); ++c) {
     const HttpChunk ch = chunks[c];
-    if (ch.first_tile + ch.ntiles > ntiles || ch.ntiles > kChunkTiles) continue;  // malformed chunk
+    if (!chunk_ok(ch, ntiles)) continue;  // malformed chunk
     const uint32_t prog = ch.prog;
     const bool real = prog < T.nprogs;
     HttpProg pg{};
@@ -639,11 +609,8 @@ __device__ __forceinline__ void http_chunks(const HttpDev& T, const uint8_t* __r
     const uint32_t tend = ch.first_tile + ch.ntiles;
     if (!walkp) {
       for (uint32_t t = ch.first_tile + wave; t < tend; t += nw) {
-        // no policy for the port → allow; unknown policy → deny; a scope
-        // without HTTP rules → allow (cilium_network_policy.h:129-138,187-191)
-        const uint32_t flags = tile_ref(tiles, ttab[t]).meta[lane].y >> 24;
-        const bool counted = !(flags & (CG_HTTP_F_PAD | CG_HTTP_F_MALFORMED));
-        out.put((size_t)t * kWave + lane, counted && (prog == kProgAllow || real) ? 1u : 0u);
+        const bool counted = slot_counted(tile_ref(tiles, ttab[t]).meta[lane].y);
+        out.put((size_t)t * kWave + lane, counted && trivial_allows(prog, real) ? 1u : 0u);
         n_allow += real && counted;
       }
     } else if (kGlobal) {

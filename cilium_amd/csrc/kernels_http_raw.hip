@@ -1002,16 +1002,7 @@ __device__ __forceinline__ uint32_t string_len(const HttpRawDev& R, const lds_u3
 template <class Tabs>
 __device__ __forceinline__ uint32_t lookup_prog(const HttpRawDev& R, const Tabs& T, uint32_t policy, bool ingress,
                                                 uint32_t port) {
-  if (policy >= R.npolicies) return kProgDeny;
-  const uint32_t key = (policy << 17) | ((uint32_t)ingress << 16) | (port & 0xFFFF);
-  uint32_t h = hash32(key) & R.phash_mask;
-  for (uint32_t probe = 0; probe <= R.phash_mask; ++probe) {
-    const uint32_t kk = T.phk[h];
-    if (kk == key) return T.phv[h];
-    if (kk == 0xFFFFFFFFu) break;
-    h = (h + 1) & R.phash_mask;
-  }
-  return T.dflt[policy * 2 + (ingress ? 1 : 0)];
+  return cg::lookup_prog(T.phk, T.phv, T.dflt, R.phash_mask, R.npolicies, policy, ingress, port);
 }
 
 template <class Tabs>
