@@ -201,6 +201,7 @@ SIGNATURES = {
     "cg_selcache_create": (C.c_int, [_u64, C.POINTER(_u32)]),
     "cg_selcache_destroy": (C.c_int, [_u64, _u32]),
     "cg_selcache_set_identities": (C.c_int, [_u64, _u32, _p, _sz, _p, _p, _p, _p, _p]),
+    "cg_selcache_set_cidr_identities": (C.c_int, [_u64, _u32, _p, _p, _sz]),
     "cg_selcache_set_rules": (C.c_int, [_u64, _u32, C.POINTER(SelectorTableC), C.POINTER(SelcacheRulesC)]),
     "cg_selcache_info": (C.c_int, [_u64, _u32, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "cg_selcache_match_dev": (C.c_int, [_u64, _u32, C.POINTER(SelectorTableC), _p, _sz, _p]),

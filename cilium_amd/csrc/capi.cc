@@ -897,7 +897,7 @@ static const ScSelTab& sc_table_of(const ScPublished& p, const cg_selector_table
 }
 
 static void sc_check_cap(const ScPublished& p, const ScSelTab& t, const void* bits, size_t cap_words) {
-  const size_t need = t.sels.size() * (size_t)p.idents->words;
+  const size_t need = t.sels.size() * (size_t)p.words;
   if (need && !bits) fail(CG_INVALID_ARGUMENT, "selcache match: NULL bits");
   if (cap_words < need) fail(CG_INVALID_ARGUMENT, "selcache match: bits holds fewer than S * W words");
 }
@@ -931,7 +931,21 @@ int cg_selcache_set_identities(uint64_t h, uint32_t sc_id, const uint32_t* ids, 
     auto snap = sc_compile_identities(ids, n, label_off, key_blob, key_off, val_blob, val_off);
     std::lock_guard<std::mutex> lk(e->mu);
     SelcacheState& s = get_sc(*e, sc_id);
+    if ((uint64_t)n + s.cidrs->recs.size() > 0xFFFFFFC0ull) fail(CG_MAP_FULL, "selector cache: too many identities");
     s.idents = std::move(snap);
+    s.dirty = true;
+  });
+}
+
+int cg_selcache_set_cidr_identities(uint64_t h, uint32_t sc_id, const uint32_t* ids, const cg_cidr* prefixes,
+                                    size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    auto snap = sc_compile_cidrs(ids, prefixes, n);
+    std::lock_guard<std::mutex> lk(e->mu);
+    SelcacheState& s = get_sc(*e, sc_id);
+    if ((uint64_t)s.idents->n + n > 0xFFFFFFC0ull) fail(CG_MAP_FULL, "selector cache: too many identities");
+    s.cidrs = std::move(snap);
     s.dirty = true;
   });
 }
@@ -954,8 +968,9 @@ int cg_selcache_info(uint64_t h, uint32_t sc_id, size_t* n_identities, size_t* w
     auto e = get(h);
     std::lock_guard<std::mutex> lk(e->mu);
     SelcacheState& s = get_sc(*e, sc_id);
-    if (n_identities) *n_identities = s.idents->n;
-    if (words) *words = s.idents->words;
+    const size_t total = (size_t)s.idents->n + s.cidrs->recs.size();
+    if (n_identities) *n_identities = total;
+    if (words) *words = (total + 63) / 64;
     if (n_selectors) *n_selectors = s.rules->sels.size();
     if (n_rules) *n_rules = s.rules->n;
   });
@@ -964,7 +979,7 @@ int cg_selcache_info(uint64_t h, uint32_t sc_id, size_t* n_identities, size_t* w
 // An ad-hoc selector table's device copy lives until the kernel reading it
 // has finished: its DevTables fence waits when the last holder lets go.
 static ScSelDev sc_upload_table(const ScSelTab& t, DevTables& tab) {
-  return ScSelDev{tab.add(t.sels), tab.add(t.reqs), tab.add(t.vals), (uint32_t)t.sels.size()};
+  return ScSelDev{tab.add(t.sels), tab.add(t.reqs), tab.add(t.vals), (uint32_t)t.sels.size(), tab.add(t.creqs)};
 }
 
 int cg_selcache_match_dev(uint64_t h, uint32_t sc_id, const cg_selector_table* sels, uint64_t* d_bits,
@@ -996,7 +1011,7 @@ int cg_selcache_match_host(uint64_t h, uint32_t sc_id, const cg_selector_table* 
     ScSelTab own;
     const ScSelTab& t = sc_table_of(*p, sels, &own);
     sc_check_cap(*p, t, bits, cap_words);
-    const size_t need = t.sels.size() * (size_t)p->idents->words;
+    const size_t need = t.sels.size() * (size_t)p->words;
     if (!need) return;
     e->set_device();
     DevTables tmp;
@@ -1020,7 +1035,7 @@ int cg_selcache_reach_dev(uint64_t h, uint32_t sc_id, const uint32_t* d_endpoint
     const auto p = sc_pub(*e, sc_id);
     e->set_device();
     void* st = stream_of(*e, stream);
-    check_launch(launch_selcache_reach(p->dR, p->idents->n, p->idents->words, d_endpoints, n,
+    check_launch(launch_selcache_reach(p->dR, p->n, p->words, d_endpoints, n,
                                        (unsigned long long*)d_ing, (unsigned long long*)d_eg, d_flags, st),
                  "selcache reach kernel launch");
     fence(p->tab, st);
@@ -1031,7 +1046,7 @@ static void sc_check_endpoints(const ScPublished& p, const uint32_t* eps, size_t
                                const void* flags) {
   if (n && (!eps || !ing || !eg || !flags)) fail(CG_INVALID_ARGUMENT, "selcache reach: NULL arrays");
   for (size_t i = 0; i < n; ++i)
-    if (eps[i] >= p.idents->n) fail(CG_INVALID_ARGUMENT, "selcache reach: endpoint index outside the identity table");
+    if (eps[i] >= p.n) fail(CG_INVALID_ARGUMENT, "selcache reach: endpoint index outside the identity table");
 }
 
 int cg_selcache_reach_host(uint64_t h, uint32_t sc_id, const uint32_t* endpoints, size_t n, uint64_t* ing,
@@ -1043,13 +1058,13 @@ int cg_selcache_reach_host(uint64_t h, uint32_t sc_id, const uint32_t* endpoints
     sc_check_endpoints(*p, endpoints, n, ing, eg, flags);
     if (!n) return;
     e->set_device();
-    const size_t W = p->idents->words, row = n * W * sizeof(uint64_t);
+    const size_t W = p->words, row = n * W * sizeof(uint64_t);
     DevMem d_ep, d_ing, d_eg, d_fl;
     d_ep.upload(endpoints, n * sizeof(uint32_t));
     d_ing.alloc(row);
     d_eg.alloc(row);
     d_fl.alloc(n);
-    check_launch(launch_selcache_reach(p->dR, p->idents->n, p->idents->words, d_ep.as<uint32_t>(), n,
+    check_launch(launch_selcache_reach(p->dR, p->n, p->words, d_ep.as<uint32_t>(), n,
                                        d_ing.as<unsigned long long>(), d_eg.as<unsigned long long>(),
                                        d_fl.as<uint8_t>(), e->stream),
                  "selcache reach kernel launch");
@@ -1072,17 +1087,17 @@ int cg_diag_selcache_match_host(uint64_t h, uint32_t sc_id, const cg_selector_ta
     ScSelTab own;
     const ScSelTab& t = sc_table_of(*p, sels, &own);
     sc_check_cap(*p, t, bits, cap_words);
-    sc_match_host(p->idents->view(), t.view(), bits, threads);
+    sc_match_host(p->host_idents(), t.view(), bits, threads);
   });
 }
 
 // The rule selectors' matrix on the host, once per snapshot.
 static void sc_ensure_host_m(Engine& e, ScPublished& p, uint32_t threads) {
   std::lock_guard<std::mutex> lk(e.mu);
-  const size_t need = p.seltab.sels.size() * (size_t)p.idents->words;
+  const size_t need = p.seltab.sels.size() * (size_t)p.words;
   if (p.host_m.size() != need || !need) {
     p.host_m.assign(std::max<size_t>(need, 1), 0);
-    sc_match_host(p.idents->view(), p.seltab.view(), p.host_m.data(), threads);
+    sc_match_host(p.host_idents(), p.seltab.view(), p.host_m.data(), threads);
     if (!need) p.host_m.resize(1);
   }
 }
@@ -1094,7 +1109,7 @@ int cg_diag_selcache_reach_host(uint64_t h, uint32_t sc_id, const uint32_t* endp
     const auto p = sc_pub(*e, sc_id);
     sc_check_endpoints(*p, endpoints, n, ing, eg, flags);
     sc_ensure_host_m(*e, *p, threads);
-    sc_reach_host(p->host_rules(), p->idents->n, p->idents->words, endpoints, n, ing, eg, flags, threads);
+    sc_reach_host(p->host_rules(), p->n, p->words, endpoints, n, ing, eg, flags, threads);
   });
 }
 
@@ -1115,8 +1130,8 @@ static ScExpDev sc_exp_view(const ScPublished& p, const ScExpRow* rows, const ui
   X.ids = ids;
   X.src = reinterpret_cast<const unsigned long long*>(src);
   X.n_rows = (uint32_t)n_rows;
-  X.n_ids = p.idents->n;
-  X.words = p.idents->words;
+  X.n_ids = p.n;
+  X.words = p.words;
   return X;
 }
 
@@ -1130,7 +1145,7 @@ int cg_selcache_expand_dev(uint64_t h, uint32_t sc_id, const cg_expand_table* ta
     if ((uintptr_t)d_keys & 7u) fail(CG_INVALID_ARGUMENT, "selcache expand: d_keys is not 8-byte aligned");
     const auto p = sc_pub(*e, sc_id);
     const ScExpTab t = sc_compile_expand(*table, src_rows);
-    if (!t.src_idx.empty() && p->idents->words && !d_src) fail(CG_INVALID_ARGUMENT, "selcache expand: NULL source matrix");
+    if (!t.src_idx.empty() && p->words && !d_src) fail(CG_INVALID_ARGUMENT, "selcache expand: NULL source matrix");
     e->set_device();
     void* st = stream_of(*e, stream);
     auto tmp = std::make_shared<DevTables>();
@@ -1170,7 +1185,7 @@ int cg_selcache_expand_host(uint64_t h, uint32_t sc_id, const cg_expand_table* t
     sc_check_expand_out(table, row_off, keys, proxy, cap_entries);
     const auto p = sc_pub(*e, sc_id);
     const ScExpTab t = sc_compile_expand(*table, src_rows);
-    const size_t src_bytes = src_rows * (size_t)p->idents->words * sizeof(uint64_t);
+    const size_t src_bytes = src_rows * (size_t)p->words * sizeof(uint64_t);
     if (src_bytes && !src) fail(CG_INVALID_ARGUMENT, "selcache expand: NULL source matrix");
     e->set_device();
     DevTables tmp;
@@ -1192,7 +1207,7 @@ static void sc_check_entries_args(const ScPublished& p, const uint32_t* eps, siz
   if (n && (!eps || !flags)) fail(CG_INVALID_ARGUMENT, "selcache entries: NULL endpoints/flags");
   if (n > 0x3FFFFFFFu) fail(CG_MAP_FULL, "selcache entries: too many endpoints");
   for (size_t i = 0; i < n; ++i)
-    if (eps[i] >= p.idents->n) fail(CG_INVALID_ARGUMENT, "selcache entries: endpoint index outside the identity table");
+    if (eps[i] >= p.n) fail(CG_INVALID_ARGUMENT, "selcache entries: endpoint index outside the identity table");
 }
 
 int cg_selcache_entries_host(uint64_t h, uint32_t sc_id, const cg_selector_table* sels, const uint32_t* endpoints,
@@ -1207,7 +1222,7 @@ int cg_selcache_entries_host(uint64_t h, uint32_t sc_id, const cg_selector_table
     sc_check_entries_args(*p, endpoints, n_endpoints, flags);
     ScSelTab own;
     if (sels) own = sc_compile_selectors(*p->idents, sc_parse_selectors(*sels));
-    const size_t S = own.sels.size(), E = n_endpoints, W = p->idents->words;
+    const size_t S = own.sels.size(), E = n_endpoints, W = p->words;
     const ScExpTab t = sc_compile_expand(*table, S + 2 * E);
     e->set_device();
     DevTables tmp;
@@ -1223,7 +1238,7 @@ int cg_selcache_entries_host(uint64_t h, uint32_t sc_id, const cg_selector_table
     if (E) {
       d_ep.upload(endpoints, E * sizeof(uint32_t));
       d_fl.alloc(E);
-      check_launch(launch_selcache_reach(p->dR, p->idents->n, p->idents->words, d_ep.as<uint32_t>(), E, src + S * W,
+      check_launch(launch_selcache_reach(p->dR, p->n, p->words, d_ep.as<uint32_t>(), E, src + S * W,
                                          src + (S + E) * W, d_fl.as<uint8_t>(), e->stream),
                    "selcache reach kernel launch");
       hip_check(hipMemcpyAsync(flags, d_fl.get(), E, hipMemcpyDeviceToHost, (hipStream_t)e->stream), "hipMemcpy D2H");
@@ -1245,9 +1260,9 @@ int cg_diag_selcache_expand_host(uint64_t h, uint32_t sc_id, const cg_expand_tab
     sc_check_expand_out(table, row_off, keys, proxy, cap_entries);
     const auto p = sc_pub(*e, sc_id);
     const ScExpTab t = sc_compile_expand(*table, src_rows);
-    if (src_rows * (size_t)p->idents->words && !src) fail(CG_INVALID_ARGUMENT, "selcache expand: NULL source matrix");
+    if (src_rows * (size_t)p->words && !src) fail(CG_INVALID_ARGUMENT, "selcache expand: NULL source matrix");
     uint64_t n = 0;
-    sc_expand_host(sc_exp_view(*p, t.rows.data(), t.src_idx.data(), t.rows.size(), p->idents->ids.data(), src),
+    sc_expand_host(sc_exp_view(*p, t.rows.data(), t.src_idx.data(), t.rows.size(), p->ids.data(), src),
                    row_off, keys, proxy, cap_entries, &n, threads);
     if (total) *total = n;
   });
@@ -1264,17 +1279,17 @@ int cg_diag_selcache_entries_host(uint64_t h, uint32_t sc_id, const cg_selector_
     sc_check_entries_args(*p, endpoints, n_endpoints, flags);
     ScSelTab own;
     if (sels) own = sc_compile_selectors(*p->idents, sc_parse_selectors(*sels));
-    const size_t S = own.sels.size(), E = n_endpoints, W = p->idents->words;
+    const size_t S = own.sels.size(), E = n_endpoints, W = p->words;
     const ScExpTab t = sc_compile_expand(*table, S + 2 * E);
     std::vector<uint64_t> src(std::max<size_t>((S + 2 * E) * W, 1), 0);
-    if (S) sc_match_host(p->idents->view(), own.view(), src.data(), threads);
+    if (S) sc_match_host(p->host_idents(), own.view(), src.data(), threads);
     if (E) {
       sc_ensure_host_m(*e, *p, threads);
-      sc_reach_host(p->host_rules(), p->idents->n, p->idents->words, endpoints, E, src.data() + S * W,
+      sc_reach_host(p->host_rules(), p->n, p->words, endpoints, E, src.data() + S * W,
                     src.data() + (S + E) * W, flags, threads);
     }
     uint64_t n = 0;
-    sc_expand_host(sc_exp_view(*p, t.rows.data(), t.src_idx.data(), t.rows.size(), p->idents->ids.data(), src.data()),
+    sc_expand_host(sc_exp_view(*p, t.rows.data(), t.src_idx.data(), t.rows.size(), p->ids.data(), src.data()),
                    row_off, keys, proxy, cap_entries, &n, threads);
     if (total) *total = n;
   });

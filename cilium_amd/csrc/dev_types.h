@@ -933,17 +933,44 @@ struct ScSel {
 };
 static_assert(sizeof(ScLabel) == 16 && sizeof(ScReq) == 16 && sizeof(ScSel) == 8, "selector cache records");
 
+// A prefix identity P/m (cg_cidr): stands for the label set GetCIDRLabels
+// gives it (pkg/labels/cidr/cidr.go:32-50) — cidr:<P masked to i>/i for i in
+// 0..m when m > 0, and reserved:world — without storing a label.  An IPv4
+// address is word 0 in host order; IPv6 is four big-endian words.
+struct ScCidr {
+  uint32_t a[4];
+  uint32_t len;     // m
+  uint32_t family;  // 4 | 6
+};
+// What a requirement can select in a prefix identity, parallel to ScReq (which
+// is full at 16 bytes): its key is the label format's exact image of the
+// prefix a/len of `family` (kScCidrPrefix), or `world` of source reserved /
+// any (kScCidrWorld: every prefix identity carries it), or neither.
+constexpr uint32_t kScCidrAbsent = 0, kScCidrWorld = 1, kScCidrPrefix = 2;
+struct ScReqCidr {
+  uint32_t a[4];
+  uint32_t mask[4];  // the first `len` bits
+  uint32_t len, family, kind;
+  uint32_t has_empty;  // "" is among the requirement's values: all implicit labels have the value ""
+};
+static_assert(sizeof(ScCidr) == 24 && sizeof(ScReqCidr) == 48, "prefix section records");
+
+// The identity table: n label identities (bits 0 .. n-1), then nc prefix
+// identities (bits n .. n+nc-1), no padding between the sections.
 struct ScIdentDev {
   const uint32_t* lab_off;  // n + 1
   const ScLabel* labels;
-  uint32_t n;      // identities
-  uint32_t words;  // ceil(n / 64)
+  uint32_t n;      // label identities
+  uint32_t words;  // ceil((n + nc) / 64)
+  const ScCidr* cidrs;
+  uint32_t nc;  // prefix identities
 };
 struct ScSelDev {
   const ScSel* sels;
   const ScReq* reqs;
   const uint32_t* vals;
   uint32_t n;  // selectors
+  const ScReqCidr* creqs;  // parallel to reqs
 };
 // A rule set over the rows of its selector table's match matrix M[n_sel][words].
 // Direction 0 = ingress, 1 = egress: req = FromRequires / ToRequires of every
@@ -999,6 +1026,33 @@ CG_HD inline bool sc_matches(const ScIdentDev& I, const ScSelDev& T, uint32_t s,
     if (found)
       for (uint32_t v = 0; v < (q.op_nv >> 8); ++v) in |= T.vals[q.vbeg + v] == got;
     if (!sc_req_holds(q.op_nv & 0xFFu, found, in)) return false;
+  }
+  return true;
+}
+
+// Whether prefix identity p/m carries the label a requirement classified as q
+// selects: the world label always; a prefix label when the families agree,
+// the requirement's prefix is no longer than the identity's, the identity is
+// not a /0 (whose only label is reserved:world) and the first q.len bits
+// agree.  Branch-free over the four words.
+CG_HD inline bool sc_cidr_found(uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, uint32_t m, uint32_t family,
+                                const ScReqCidr& q) {
+  const uint32_t diff = ((p0 ^ q.a[0]) & q.mask[0]) | ((p1 ^ q.a[1]) & q.mask[1]) | ((p2 ^ q.a[2]) & q.mask[2]) |
+                        ((p3 ^ q.a[3]) & q.mask[3]);
+  const bool prefix = (q.kind == kScCidrPrefix) & (family == q.family) & (q.len <= m) & (m > 0) & (diff == 0);
+  return (q.kind == kScCidrWorld) | prefix;
+}
+
+// Selector s against prefix identity c (the host walker; the kernel does the
+// same with the record in registers).
+CG_HD inline bool sc_cidr_matches(const ScIdentDev& I, const ScSelDev& T, uint32_t s, uint32_t c) {
+  const ScSel h = T.sels[s];
+  if (h.nreq & kScAlways) return true;
+  const ScCidr p = I.cidrs[c];
+  for (uint32_t r = h.rbeg; r < h.rbeg + h.nreq; ++r) {
+    const ScReqCidr q = T.creqs[r];
+    const bool found = sc_cidr_found(p.a[0], p.a[1], p.a[2], p.a[3], p.len, p.family, q);
+    if (!sc_req_holds(T.reqs[r].op_nv & 0xFFu, found, found && q.has_empty)) return false;
   }
   return true;
 }

@@ -101,7 +101,9 @@ int launch_http_ring(const HttpDev& HT, const HttpRawDev& R, const HttpRingDev& 
 int ring_clock(unsigned long long* d_out, void* stream);
 
 // The selector cache (kernels_selcache.hip).  bits[T.n][I.words]: one ballot
-// word per (selector, 64-identity group), padding bits zero.
+// word per (selector, 64-identity group), padding bits zero.  The label
+// section's whole words come from selcache_match_kernel; with a prefix section
+// (I.nc) the words from I.n / 64 on come from selcache_cidr_match_kernel.
 int launch_selcache_match(const ScIdentDev& I, const ScSelDev& T, unsigned long long* bits, void* stream, int cus);
 // ing/eg[n][words], flags[n] for the endpoints eps[n] (identity indices; an
 // index >= n_ids yields zero rows).  R.M is the rule selectors' match matrix.

@@ -14,6 +14,19 @@
 // on registers; memory traffic is the label records once per block and chunk
 // and one 8-byte word per (selector, wave).
 //
+// selcache_cidr_match_kernel: the same for the prefix section (ScCidr), whose
+// identities stand for GetCIDRLabels' label set without storing it.  One lane
+// per prefix identity with its 24-byte record in registers; per requirement
+// the classification record (ScReqCidr: address, mask words, length, family,
+// kind) comes through scalar loads and the test is sc_cidr_found — a masked
+// XOR over four words and two compares, no branch — followed by the label
+// kernel's sc_req_holds.  No LDS, no atomics, no scratch.  The word in which
+// the label section ends belongs to this kernel alone: its grid starts at
+// word N / 64 and the label lanes of that one wave go through sc_matches, the
+// host walker's label path, so the word is written once and whole, and the
+// label kernel (which stops before it) and this one never store to the same
+// address.
+//
 // selcache_reach_kernel: one block per (endpoint, 256 words).  The rules are
 // taken in tiles: the block first ballots, per 64 rules, whether the rule's
 // subject row has the endpoint's bit (the rule is "selected"), leaving one
@@ -60,7 +73,9 @@ __global__ __launch_bounds__(kMatchThreads) void selcache_match_kernel(ScIdentDe
                                                                        unsigned long long* __restrict__ bits) {
   const uint32_t i = blockIdx.x * kMatchThreads + threadIdx.x;
   const uint32_t w = uni(i >> 6);  // this wave's word: 64 consecutive identities
-  if (w >= I.words) return;        // whole waves past the table (nothing below synchronises the block)
+  // whole waves past the section (nothing below synchronises the block); with a
+  // prefix section the word the labels end in is selcache_cidr_match_kernel's
+  if (w >= (I.nc ? I.n >> 6 : I.words)) return;
   const bool valid = i < I.n;
   uint32_t lo = 0, nl = 0;
   if (valid) {
@@ -117,6 +132,49 @@ __global__ __launch_bounds__(kMatchThreads) void selcache_match_kernel(ScIdentDe
         if (__ballot(m) == 0ull) break;  // no identity of the wave can still match
       }
     }
+    const unsigned long long word = __ballot(m);  // lanes past the table vote 0: zero padding bits
+    if ((threadIdx.x & 63u) == 0) bits[(size_t)su * I.words + w] = word;
+  }
+}
+
+__global__ __launch_bounds__(kMatchThreads) void selcache_cidr_match_kernel(ScIdentDev I, ScSelDev T, uint32_t chunk,
+                                                                            unsigned long long* __restrict__ bits) {
+  const uint32_t w0 = I.n >> 6;  // the first word with prefix bits
+  const unsigned long long i = ((unsigned long long)w0 << 6) + (unsigned long long)blockIdx.x * kMatchThreads + threadIdx.x;  // bit index
+  if ((i >> 6) >= I.words) return;  // whole waves past the table
+  const uint32_t w = uni((uint32_t)(i >> 6));
+  const bool is_label = i < I.n;  // only in the wave of word w0, when the label section ends inside it
+  const bool mixed = w == w0 && (I.n & 63u);
+  const bool valid = !is_label && i - I.n < I.nc;
+  uint32_t p0 = 0, p1 = 0, p2 = 0, p3 = 0, plen = 0, pfam = 0;
+  if (valid) {
+    const uint2* rec = reinterpret_cast<const uint2*>(I.cidrs + (i - I.n));
+    const uint2 x = rec[0], y = rec[1], z = rec[2];
+    p0 = x.x, p1 = x.y, p2 = y.x, p3 = y.y, plen = z.x, pfam = z.y;
+  }
+  const uint32_t s0 = blockIdx.y * chunk;
+  const uint32_t s1 = s0 + chunk < T.n ? s0 + chunk : T.n;
+  for (uint32_t s = s0; s < s1; ++s) {
+    const uint32_t su = uni(s);
+    const ScSel h = T.sels[su];
+    bool m = valid;
+    if (!(h.nreq & kScAlways)) {
+      const uint32_t nreq = uni(h.nreq), rbeg = uni(h.rbeg);
+      for (uint32_t r = 0; r < nreq; ++r) {
+        const uint32_t ri = uni(rbeg + r);
+        const uint32_t op = uni(T.reqs[ri].op_nv) & 0xFFu;
+        const uint4* cq = reinterpret_cast<const uint4*>(T.creqs + ri);
+        const uint4 qa = cq[0], qm = cq[1], qk = cq[2];
+        ScReqCidr q;
+        q.a[0] = uni(qa.x), q.a[1] = uni(qa.y), q.a[2] = uni(qa.z), q.a[3] = uni(qa.w);
+        q.mask[0] = uni(qm.x), q.mask[1] = uni(qm.y), q.mask[2] = uni(qm.z), q.mask[3] = uni(qm.w);
+        q.len = uni(qk.x), q.family = uni(qk.y), q.kind = uni(qk.z), q.has_empty = uni(qk.w);
+        const bool found = sc_cidr_found(p0, p1, p2, p3, plen, pfam, q);
+        m = m && sc_req_holds(op, found, found && q.has_empty);
+        if (__ballot(m) == 0ull) break;  // no prefix identity of the wave can still match
+      }
+    }
+    if (mixed && is_label) m = sc_matches(I, T, su, (uint32_t)i);
     const unsigned long long word = __ballot(m);  // lanes past the table vote 0: zero padding bits
     if ((threadIdx.x & 63u) == 0) bits[(size_t)su * I.words + w] = word;
   }
@@ -316,17 +374,35 @@ int launch_selcache_expand(const ScExpDev& X, unsigned long long* row_off, void*
 }
 
 int launch_selcache_match(const ScIdentDev& I, const ScSelDev& T, unsigned long long* bits, void* stream, int cus) {
-  if (I.n == 0 || T.n == 0) return 0;
-  const uint32_t gx = (I.n + kMatchThreads - 1) / kMatchThreads;
+  if (T.n == 0) return 0;
   // selectors per block: as many as keeps every CU busy with a few blocks,
   // and few enough blocks for the grid's y extent
-  uint32_t chunk = kMatchChunk;
-  const uint64_t want = 4ull * (uint64_t)(cus > 0 ? cus : 1);
-  while (chunk > 16 && (uint64_t)gx * ((T.n + chunk - 1) / chunk) < want) chunk >>= 1;
-  while ((T.n + chunk - 1) / chunk > 65535u) chunk <<= 1;
-  const dim3 g(gx, (T.n + chunk - 1) / chunk), b(kMatchThreads);
-  hipLaunchKernelGGL(selcache_match_kernel, g, b, 0, (hipStream_t)stream, I, T, chunk, bits);
-  return (int)hipGetLastError();
+  auto chunk_of = [&](uint32_t gx) {
+    uint32_t chunk = kMatchChunk;
+    const uint64_t want = 4ull * (uint64_t)(cus > 0 ? cus : 1);
+    while (chunk > 16 && (uint64_t)gx * ((T.n + chunk - 1) / chunk) < want) chunk >>= 1;
+    while ((T.n + chunk - 1) / chunk > 65535u) chunk <<= 1;
+    return chunk;
+  };
+  // the label section's whole words (all of its words without a prefix section)
+  const uint32_t lwords = I.nc ? I.n >> 6 : I.words;
+  if (lwords) {
+    const uint32_t gx = (uint32_t)(((uint64_t)lwords * 64 + kMatchThreads - 1) / kMatchThreads);
+    const uint32_t chunk = chunk_of(gx);
+    const dim3 g(gx, (T.n + chunk - 1) / chunk), b(kMatchThreads);
+    hipLaunchKernelGGL(selcache_match_kernel, g, b, 0, (hipStream_t)stream, I, T, chunk, bits);
+    const int err = (int)hipGetLastError();
+    if (err) return err;
+  }
+  if (I.nc) {  // from the word the label section ends in to the last
+    const uint64_t lanes = (uint64_t)(I.words - (I.n >> 6)) * 64;
+    const uint32_t gx = (uint32_t)((lanes + kMatchThreads - 1) / kMatchThreads);
+    const uint32_t chunk = chunk_of(gx);
+    const dim3 g(gx, (T.n + chunk - 1) / chunk), b(kMatchThreads);
+    hipLaunchKernelGGL(selcache_cidr_match_kernel, g, b, 0, (hipStream_t)stream, I, T, chunk, bits);
+    return (int)hipGetLastError();
+  }
+  return 0;
 }
 
 int launch_selcache_reach(const ScRuleDev& R, uint32_t n_ids, uint32_t words, const uint32_t* eps, size_t n,

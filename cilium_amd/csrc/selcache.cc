@@ -71,7 +71,217 @@ void run_threads(size_t items, uint32_t threads, F&& f) {
   for (auto& th : pool) th.join();
 }
 
+// ---- the label format of a prefix (pkg/labels/cidr.go:23-45)
+// net.IP.String() of a 16-byte address that To4() refuses: lower-case hex
+// groups without leading zeros, the first longest run of two or more zero
+// groups as "::".
+std::string go_ip6_string(const uint8_t p[16]) {
+  int e0 = -1, e1 = -1;
+  for (int i = 0; i < 16; i += 2) {
+    int j = i;
+    while (j < 16 && p[j] == 0 && p[j + 1] == 0) j += 2;
+    if (j > i && j - i > e1 - e0) {
+      e0 = i;
+      e1 = j;
+      i = j;
+    }
+  }
+  if (e1 - e0 <= 2) e0 = e1 = -1;
+  static const char* hex = "0123456789abcdef";
+  std::string out;
+  for (int i = 0; i < 16; i += 2) {
+    if (i == e0) {
+      out += "::";
+      i = e1;
+      if (i >= 16) break;
+    } else if (i > 0) {
+      out += ':';
+    }
+    const uint32_t g = ((uint32_t)p[i] << 8) | p[i + 1];
+    bool on = false;
+    for (int sh = 12; sh >= 0; sh -= 4) {
+      const uint32_t d = (g >> sh) & 15u;
+      if (d || on || sh == 0) {
+        out += hex[d];
+        on = true;
+      }
+    }
+  }
+  return out;
+}
+
+bool is_mapped4(const uint8_t p[16]) {  // net.IP.To4 on 16 bytes
+  for (int i = 0; i < 10; ++i)
+    if (p[i]) return false;
+  return p[10] == 0xFF && p[11] == 0xFF;
+}
+
+std::string dotted(const uint8_t* p) {
+  return std::to_string(p[0]) + "." + std::to_string(p[1]) + "." + std::to_string(p[2]) + "." + std::to_string(p[3]);
+}
+
+// maskedIPToLabelString without the "cidr:" source.
+std::string label_key_of(uint32_t family, const uint8_t addr[16], uint32_t len) {
+  std::string ip = family == 4 ? dotted(addr) : is_mapped4(addr) ? dotted(addr + 12) : go_ip6_string(addr);
+  for (char& c : ip)
+    if (c == ':') c = '-';
+  if (ip.front() == '-') ip.insert(ip.begin(), '0');
+  if (ip.back() == '-') ip.push_back('0');
+  return ip + "/" + std::to_string(len);
+}
+
+bool parse_dec(const std::string& s, size_t lo, size_t hi, uint32_t max, uint32_t* out) {
+  if (hi <= lo || hi - lo > 3) return false;
+  uint32_t v = 0;
+  for (size_t i = lo; i < hi; ++i) {
+    if (s[i] < '0' || s[i] > '9') return false;
+    v = v * 10 + (uint32_t)(s[i] - '0');
+  }
+  *out = v;
+  return v <= max;
+}
+
+bool parse_ip4(const std::string& s, uint8_t out[4]) {
+  size_t at = 0;
+  for (int k = 0; k < 4; ++k) {
+    size_t dot = k < 3 ? s.find('.', at) : s.size();
+    uint32_t v;
+    if (dot == std::string::npos || !parse_dec(s, at, dot, 255, &v)) return false;
+    out[k] = (uint8_t)v;
+    at = dot + 1;
+  }
+  return true;
+}
+
+// Hex groups and at most one "::"; no embedded dotted quad (the label format
+// never prints one inside an IPv6 text).
+bool parse_ip6(const std::string& s, uint8_t out[16]) {
+  uint16_t g[8];
+  int ng = 0, ell = -1;
+  size_t i = 0;
+  const size_t n = s.size();
+  if (n >= 2 && s[0] == ':' && s[1] == ':') {
+    ell = 0;
+    i = 2;
+  } else if (n == 0 || s[0] == ':') {
+    return false;
+  }
+  while (i < n) {
+    uint32_t v = 0;
+    size_t d = 0;
+    for (; i < n && d < 4; ++i, ++d) {
+      const char c = s[i];
+      const int x = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+      if (x < 0) break;
+      v = v * 16 + (uint32_t)x;
+    }
+    if (d == 0 || ng == 8) return false;
+    g[ng++] = (uint16_t)v;
+    if (i == n) break;
+    if (s[i] != ':' || ++i == n) return false;
+    if (s[i] == ':') {
+      if (ell >= 0) return false;
+      ell = ng;
+      ++i;
+    }
+  }
+  if (ell < 0 ? ng != 8 : ng > 7) return false;
+  uint16_t full[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int head = ell < 0 ? ng : ell;
+  for (int k = 0; k < head; ++k) full[k] = g[k];
+  for (int k = head; k < ng; ++k) full[8 - (ng - k)] = g[k];
+  for (int k = 0; k < 8; ++k) {
+    out[2 * k] = (uint8_t)(full[k] >> 8);
+    out[2 * k + 1] = (uint8_t)full[k];
+  }
+  return true;
+}
+
+uint32_t mask_word(uint32_t len, uint32_t k) {  // bits of word k among the first `len`
+  const uint32_t b = len > 32 * k ? std::min<uint32_t>(len - 32 * k, 32) : 0;
+  return b ? 0xFFFFFFFFu << (32 - b) : 0u;
+}
+
+uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+
 }  // namespace
+
+std::string sc_cidr_label_key(const ScCidr& p) {
+  uint8_t addr[16];
+  for (int k = 0; k < 4; ++k)
+    for (int b = 0; b < 4; ++b) addr[4 * k + b] = (uint8_t)(p.a[k] >> (24 - 8 * b));
+  return label_key_of(p.family, addr, p.len);
+}
+
+std::shared_ptr<const ScCidrSnap> sc_compile_cidrs(const uint32_t* ids, const cg_cidr* prefixes, size_t n) {
+  auto s = std::make_shared<ScCidrSnap>();
+  if (n == 0) return s;
+  if (!ids || !prefixes) fail(CG_INVALID_ARGUMENT, "selector cache: NULL prefix identity arrays");
+  if (n > 0xFFFFFFC0u) fail(CG_MAP_FULL, "selector cache: too many identities");
+  s->ids.assign(ids, ids + n);
+  s->recs.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    const cg_cidr& c = prefixes[i];
+    if (c.family != 4 && c.family != 6)
+      fail(CG_INVALID_ARGUMENT, "prefix identity " + std::to_string(i) + ": family is neither 4 nor 6");
+    if (c.prefixlen > (c.family == 4 ? 32u : 128u))
+      fail(CG_INVALID_ARGUMENT, "prefix identity " + std::to_string(i) + ": prefix length past the family's");
+    ScCidr r{};
+    const uint32_t nw = c.family == 4 ? 1 : 4;
+    for (uint32_t k = 0; k < nw; ++k) r.a[k] = be32(c.addr + 4 * k) & mask_word(c.prefixlen, k);
+    r.len = c.prefixlen;
+    r.family = c.family;
+    s->recs[i] = r;
+  }
+  return s;
+}
+
+ScReqCidr sc_classify_req(const std::string& src, const std::string& key, const std::vector<std::string>& vals) {
+  ScReqCidr q{};
+  q.kind = kScCidrAbsent;
+  for (const auto& v : vals) q.has_empty |= v.empty() ? 1u : 0u;
+  if (key == "world" && (src == "reserved" || src == "any")) {
+    q.kind = kScCidrWorld;
+    return q;
+  }
+  if (src != "cidr" && src != "any") return q;
+  const size_t slash = key.rfind('/');
+  uint32_t len;
+  if (slash == std::string::npos || !parse_dec(key, slash + 1, key.size(), 128, &len)) return q;
+  std::string ip = key.substr(0, slash);
+  uint8_t addr[16] = {0};
+  uint32_t family;
+  if (ip.find('.') != std::string::npos) {
+    uint8_t v4[4];
+    if (!parse_ip4(ip, v4)) return q;
+    if (len <= 32) {
+      family = 4;
+      std::copy(v4, v4 + 4, addr);
+    } else if (len >= 96) {  // the text of an IPv4-mapped IPv6 prefix
+      family = 6;
+      addr[10] = addr[11] = 0xFF;
+      std::copy(v4, v4 + 4, addr + 12);
+    } else {
+      return q;
+    }
+  } else {
+    for (char& c : ip)
+      if (c == '-') c = ':';
+    if (!parse_ip6(ip, addr)) return q;
+    family = 6;
+  }
+  const uint32_t nw = family == 4 ? 1 : 4;
+  for (uint32_t k = 0; k < nw; ++k) {
+    q.a[k] = be32(addr + 4 * k);
+    q.mask[k] = mask_word(len, k);
+    if (q.a[k] & ~q.mask[k]) return q;  // host bits set: no label is printed that way
+  }
+  if (label_key_of(family, addr, len) != key) return q;
+  q.len = len;
+  q.family = family;
+  q.kind = kScCidrPrefix;
+  return q;
+}
 
 std::shared_ptr<const ScIdentSnap> sc_compile_identities(const uint32_t* ids, size_t n, const uint32_t* label_off,
                                                          const uint8_t* key_blob, const uint64_t* key_off,
@@ -99,7 +309,6 @@ std::shared_ptr<const ScIdentSnap> sc_compile_identities(const uint32_t* ids, si
                            0};
   }
   s->n = (uint32_t)n;
-  s->words = (uint32_t)((n + 63) / 64);
   return s;
 }
 
@@ -209,6 +418,7 @@ ScSelTab sc_compile_selectors(const ScIdentSnap& idents, const std::vector<ScSel
       if (t.vals.size() + q.vals.size() > 0xFFFFFFF0u) fail(CG_MAP_FULL, "selector table: too many values");
       t.reqs.push_back(ScReq{id_of(q.key), id_of(q.src), (uint32_t)q.op | ((uint32_t)q.vals.size() << 8),
                              (uint32_t)t.vals.size()});
+      t.creqs.push_back(sc_classify_req(q.src, q.key, q.vals));
       for (const auto& v : q.vals) t.vals.push_back(id_of(v));
     }
   }
@@ -221,8 +431,9 @@ void sc_match_host(const ScIdentDev& I, const ScSelDev& T, uint64_t* bits, uint3
     for (size_t c = lo; c < hi; ++c) {
       const uint32_t s = (uint32_t)(c / W), w = (uint32_t)(c % W);
       uint64_t word = 0;
-      const uint32_t i1 = std::min<uint64_t>(I.n, 64ull * w + 64);
-      for (uint32_t i = 64 * w; i < i1; ++i) word |= (uint64_t)sc_matches(I, T, s, i) << (i & 63u);
+      const uint32_t i1 = std::min<uint64_t>((uint64_t)I.n + I.nc, 64ull * w + 64);
+      for (uint32_t i = 64 * w; i < i1; ++i)
+        word |= (uint64_t)(i < I.n ? sc_matches(I, T, s, i) : sc_cidr_matches(I, T, s, i - I.n)) << (i & 63u);
       bits[c] = word;
     }
   });
@@ -343,15 +554,23 @@ ScRuleDev ScPublished::host_rules() const {
 void SelcacheState::rebuild(Engine& e) {
   auto p = std::make_shared<ScPublished>();
   p->idents = idents;
+  p->cidrs = cidrs;
   p->rules = rules;
+  const uint64_t total = (uint64_t)idents->n + cidrs->recs.size();
+  if (total > 0xFFFFFFC0ull) fail(CG_MAP_FULL, "selector cache: too many identities");
+  p->n = (uint32_t)total;
+  p->words = (uint32_t)((total + 63) / 64);
+  p->ids = idents->ids;
+  p->ids.insert(p->ids.end(), cidrs->ids.begin(), cidrs->ids.end());
   p->seltab = sc_compile_selectors(*idents, rules->sels);
   if (e.has_gpu()) {
     e.set_device();
     auto tab = std::make_shared<DevTables>();
-    p->dI = ScIdentDev{tab->add(idents->lab_off), tab->add(idents->labels), idents->n, idents->words};
-    p->d_ids = tab->add(idents->ids);
+    p->dI = ScIdentDev{tab->add(idents->lab_off), tab->add(idents->labels), idents->n, p->words,
+                       tab->add(cidrs->recs),     (uint32_t)cidrs->recs.size()};
+    p->d_ids = tab->add(p->ids);
     p->dT = ScSelDev{tab->add(p->seltab.sels), tab->add(p->seltab.reqs), tab->add(p->seltab.vals),
-                     (uint32_t)p->seltab.sels.size()};
+                     (uint32_t)p->seltab.sels.size(), tab->add(p->seltab.creqs)};
     ScRuleDev r{};
     r.subject = tab->add(rules->subject);
     r.flags = tab->add(rules->flags);
@@ -363,7 +582,7 @@ void SelcacheState::rebuild(Engine& e) {
     }
     r.n = rules->n;
     tab->bufs.emplace_back();
-    tab->bufs.back().alloc((size_t)p->dT.n * idents->words * sizeof(uint64_t));
+    tab->bufs.back().alloc((size_t)p->dT.n * p->words * sizeof(uint64_t));
     unsigned long long* M = tab->bufs.back().as<unsigned long long>();
     r.M = M;
     hip_check(launch_selcache_match(p->dI, p->dT, M, e.stream, e.cus), "selcache match kernel launch");

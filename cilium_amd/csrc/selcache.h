@@ -23,8 +23,15 @@ struct ScIdentSnap {
   std::vector<uint32_t> lab_off{0};
   std::vector<ScLabel> labels;
   std::unordered_map<std::string, uint32_t> dict;  // ids from 1; "any" is kScAny and not stored
-  uint32_t n = 0, words = 0;
-  ScIdentDev view() const { return {lab_off.data(), labels.data(), n, words}; }
+  uint32_t n = 0;
+};
+
+// The prefix section: identities that are a CIDR prefix, as 24-byte records
+// in the given order (cg_selcache_set_cidr_identities); their bits follow the
+// label identities'.
+struct ScCidrSnap {
+  std::vector<uint32_t> ids;
+  std::vector<ScCidr> recs;
 };
 
 // Selectors as given (strings), kept so they can be interned again when the
@@ -43,7 +50,8 @@ struct ScSelTab {
   std::vector<ScSel> sels;
   std::vector<ScReq> reqs;
   std::vector<uint32_t> vals;
-  ScSelDev view() const { return {sels.data(), reqs.data(), vals.data(), (uint32_t)sels.size()}; }
+  std::vector<ScReqCidr> creqs;  // parallel to reqs: what each requirement selects in a prefix identity
+  ScSelDev view() const { return {sels.data(), reqs.data(), vals.data(), (uint32_t)sels.size(), creqs.data()}; }
 };
 
 struct ScRuleSrc {
@@ -59,10 +67,21 @@ struct ScRuleSrc {
 std::shared_ptr<const ScIdentSnap> sc_compile_identities(const uint32_t* ids, size_t n, const uint32_t* label_off,
                                                          const uint8_t* key_blob, const uint64_t* key_off,
                                                          const uint8_t* val_blob, const uint64_t* val_off);
+// Validates family and prefix length (CG_INVALID_ARGUMENT) and masks the
+// address bits below the prefix.
+std::shared_ptr<const ScCidrSnap> sc_compile_cidrs(const uint32_t* ids, const cg_cidr* prefixes, size_t n);
+// What a requirement on `src:key` with `vals` selects in a prefix identity:
+// the key must be the exact image of a prefix under the label format
+// (maskedIPToLabelString, pkg/labels/cidr.go:23-45) — inverted, re-serialised
+// as Go's net.IP.String() prints it and compared as strings — or `world`.
+ScReqCidr sc_classify_req(const std::string& src, const std::string& key, const std::vector<std::string>& vals);
+// The key part of the label cidr:<P>/<m> of a (masked) prefix record.
+std::string sc_cidr_label_key(const ScCidr& p);
 std::vector<ScSelSrc> sc_parse_selectors(const cg_selector_table& t);
 std::shared_ptr<const ScRuleSrc> sc_parse_rules(const cg_selector_table& sels, const cg_selcache_rules& rules);
 // Interns against the identities' dictionary; a string no identity carries
-// gets an id past the dictionary's.
+// gets an id past the dictionary's.  Each requirement is also classified for
+// the prefix section (sc_classify_req).
 ScSelTab sc_compile_selectors(const ScIdentSnap& idents, const std::vector<ScSelSrc>& sels);
 
 // Host walkers over the compiled tables (cg_diag_selcache_*): what the
@@ -88,19 +107,27 @@ void sc_expand_host(const ScExpDev& X, uint64_t* row_off, cg_policy_key* keys, u
 // copies with the rule selectors' match matrix M already computed.
 struct ScPublished {
   std::shared_ptr<const ScIdentSnap> idents;
+  std::shared_ptr<const ScCidrSnap> cidrs;
   std::shared_ptr<const ScRuleSrc> rules;
+  std::vector<uint32_t> ids;      // both sections' identity numbers, in bit order
+  uint32_t n = 0, words = 0;      // identities of both sections; ceil(n / 64)
+  ScIdentDev host_idents() const {
+    return {idents->lab_off.data(), idents->labels.data(), idents->n, words, cidrs->recs.data(),
+            (uint32_t)cidrs->recs.size()};
+  }
   ScSelTab seltab;                // rules->sels interned against idents
   std::vector<uint64_t> host_m;   // M on the host, filled by the first diag reach
   std::shared_ptr<DevTables> tab; // device copies (engine.h)
   ScIdentDev dI{};
   ScSelDev dT{};
   ScRuleDev dR{};
-  const uint32_t* d_ids = nullptr;  // idents->ids on the device: what expansion writes as sec_label
+  const uint32_t* d_ids = nullptr;  // ids on the device: what expansion writes as sec_label
   ScRuleDev host_rules() const;   // over host_m
 };
 
 struct SelcacheState {
   std::shared_ptr<const ScIdentSnap> idents = std::make_shared<ScIdentSnap>();
+  std::shared_ptr<const ScCidrSnap> cidrs = std::make_shared<ScCidrSnap>();
   std::shared_ptr<const ScRuleSrc> rules = std::make_shared<ScRuleSrc>();
   bool dirty = true;
   std::shared_ptr<ScPublished> pub;

@@ -38,6 +38,8 @@ import functools
 from dataclasses import dataclass, field
 from typing import Iterable, Mapping, Optional
 
+from . import cidr as _cidr
+from .cidr import CIDRRule
 from .policy import (L7Rules, PolicyKey, PortRuleHTTP, PortRuleKafka, TrafficDirection, get_http_rule, go_fields,
                      htons, port_network_policy_rule)
 
@@ -547,6 +549,16 @@ def parse_port(port: str) -> int:
     return v
 
 
+def cidr_selectors(cidrs) -> list:
+    """CIDRSlice.GetAsEndpointSelectors (api/cidr.go:70-86)."""
+    return [EndpointSelector.of(d) for d in _cidr.cidr_slice_selectors(cidrs)] if cidrs else []
+
+
+def cidr_rule_selectors(rules) -> list:
+    """CIDRRuleSlice.GetAsEndpointSelectors (api/cidr.go:99-104)."""
+    return [EndpointSelector.of(d) for d in _cidr.cidr_rule_slice_selectors(rules)] if rules else []
+
+
 @dataclass
 class PortRule:
     """api.PortRule (api/l4.go:44-60)."""
@@ -556,45 +568,56 @@ class PortRule:
 
 @dataclass
 class IngressRule:
-    """api.IngressRule (api/ingress.go); CIDR members are kept only to be
-    refused by the label-based resolution (not on this path)."""
+    """api.IngressRule (api/ingress.go): FromCIDR holds CIDR strings,
+    FromCIDRSet CIDRRule objects."""
     FromEndpoints: list = field(default_factory=list)
     FromRequires: list = field(default_factory=list)
     FromEntities: list = field(default_factory=list)
     ToPorts: list = field(default_factory=list)
     FromCIDR: list = field(default_factory=list)
+    FromCIDRSet: list = field(default_factory=list)
 
     def source_selectors(self) -> list:
-        """GetSourceEndpointSelectors (ingress.go:111-115)."""
+        """GetSourceEndpointSelectors (ingress.go:111-115): FromEndpoints,
+        the entities, FromCIDR, FromCIDRSet."""
         out = list(self.FromEndpoints)
         for e in self.FromEntities:
             out += _ENTITY_SELECTORS.get(e, [])
+        out += cidr_selectors(self.FromCIDR)
+        out += cidr_rule_selectors(self.FromCIDRSet)
         return out
 
     def is_label_based(self) -> bool:
         """IsLabelBased (ingress.go:120-122)."""
-        return not self.FromRequires and not self.FromCIDR
+        return not self.FromRequires and not self.FromCIDR and not self.FromCIDRSet
 
 
 @dataclass
 class EgressRule:
-    """api.EgressRule (api/egress.go)."""
+    """api.EgressRule (api/egress.go): ToCIDR holds CIDR strings, ToCIDRSet
+    CIDRRule objects; ToServices is kept only for IsLabelBased (services are
+    not translated here)."""
     ToEndpoints: list = field(default_factory=list)
     ToRequires: list = field(default_factory=list)
     ToEntities: list = field(default_factory=list)
     ToPorts: list = field(default_factory=list)
     ToCIDR: list = field(default_factory=list)
+    ToCIDRSet: list = field(default_factory=list)
+    ToServices: list = field(default_factory=list)
 
     def destination_selectors(self) -> list:
-        """GetDestinationEndpointSelectors (egress.go:139-143)."""
+        """GetDestinationEndpointSelectors (egress.go:139-143): ToEndpoints,
+        the entities, ToCIDR, ToCIDRSet."""
         out = list(self.ToEndpoints)
         for e in self.ToEntities:
             out += _ENTITY_SELECTORS.get(e, [])
+        out += cidr_selectors(self.ToCIDR)
+        out += cidr_rule_selectors(self.ToCIDRSet)
         return out
 
     def is_label_based(self) -> bool:
         """IsLabelBased (egress.go:148-150)."""
-        return not self.ToRequires and not self.ToCIDR
+        return not self.ToRequires and not self.ToCIDR and not self.ToCIDRSet and not self.ToServices
 
 
 @dataclass
@@ -619,12 +642,14 @@ class Rule:
         ing = [IngressRule([selector_from_json(x) for x in r.get("fromendpoints") or []],
                            [selector_from_json(x) for x in r.get("fromrequires") or []],
                            list(r.get("fromentities") or []), ports(r.get("toports")),
-                           list(r.get("fromcidr") or []) + list(r.get("fromcidrset") or []))
+                           [str(x) for x in r.get("fromcidr") or []],
+                           [CIDRRule.from_json(x) for x in r.get("fromcidrset") or []])
                for r in map(go_fields, d.get("ingress") or [])]
         eg = [EgressRule([selector_from_json(x) for x in r.get("toendpoints") or []],
                          [selector_from_json(x) for x in r.get("torequires") or []],
                          list(r.get("toentities") or []), ports(r.get("toports")),
-                         list(r.get("tocidr") or []) + list(r.get("tocidrset") or []) +
+                         [str(x) for x in r.get("tocidr") or []],
+                         [CIDRRule.from_json(x) for x in r.get("tocidrset") or []],
                          list(r.get("toservices") or []))
               for r in map(go_fields, d.get("egress") or [])]
         labels = tuple(sorted(str(x) for x in d.get("labels") or []))
@@ -634,7 +659,19 @@ class Rule:
         """Rule.Sanitize (rule_validation.go:37-69, :316-358): every port
         parses as a non-zero uint16, protocols are normalised (ParseL4Proto),
         L7 rules only on TCP, at most 40 ports per PortRule, L7 rule
-        validation (PortRuleHTTP / PortRuleKafka Sanitize)."""
+        validation (PortRuleHTTP / PortRuleKafka Sanitize).  The CIDR members
+        go through IngressRule.sanitize / EgressRule.sanitize's CIDR checks
+        (cidr.sanitize_direction)."""
+        for i in self.Ingress:
+            _cidr.sanitize_direction({"FromEndpoints": len(i.FromEndpoints), "FromCIDR": len(i.FromCIDR),
+                                      "FromCIDRSet": len(i.FromCIDRSet), "FromEntities": len(i.FromEntities)},
+                                     ("FromCIDR", "FromCIDRSet"), bool(i.ToPorts), i.FromCIDR, i.FromCIDRSet,
+                                     "ingress")
+        for e in self.Egress:
+            _cidr.sanitize_direction({"ToCIDR": len(e.ToCIDR), "ToCIDRSet": len(e.ToCIDRSet),
+                                      "ToEndpoints": len(e.ToEndpoints), "ToEntities": len(e.ToEntities),
+                                      "ToServices": len(e.ToServices)},
+                                     (), bool(e.ToPorts), e.ToCIDR, e.ToCIDRSet, "egress")
         for rs in (self.Ingress, self.Egress):
             for r in rs:
                 for pr in r.ToPorts:
@@ -781,7 +818,7 @@ def resolve_rule_l4_ingress(r: Rule, to_labels, requirements: tuple, result: L4P
     for ing in r.Ingress:
         if requirements:
             ing = IngressRule([with_requirements(sel, requirements) for sel in ing.FromEndpoints], ing.FromRequires,
-                              ing.FromEntities, ing.ToPorts, ing.FromCIDR)
+                              ing.FromEntities, ing.ToPorts, ing.FromCIDR, ing.FromCIDRSet)
         peers = ing.source_selectors()
         if from_labels is not None and ing.ToPorts and peers and not any(p.matches(from_labels) for p in peers):
             continue
@@ -797,7 +834,7 @@ def resolve_rule_l4_egress(r: Rule, from_labels, requirements: tuple, result: L4
     for eg in r.Egress:
         if requirements:
             eg = EgressRule([with_requirements(sel, requirements) for sel in eg.ToEndpoints], eg.ToRequires,
-                            eg.ToEntities, eg.ToPorts, eg.ToCIDR)
+                            eg.ToEntities, eg.ToPorts, eg.ToCIDR, eg.ToCIDRSet, eg.ToServices)
         peers = eg.destination_selectors()
         found += _merge_l4(peers, [], eg.ToPorts, r.Labels, result.Egress, False)
     return result if found else None

@@ -15,7 +15,10 @@ kernels over the whole identity cache:
   (``cg_selcache_expand_*``, ``cg_selcache_entries_host``) and applied with
   one ``PolicyMap.sync`` per map — no Python object per entry;
 * ``endpoint_policy_map_states``: the dicts ``resolve.endpoint_policy_map_state``
-  returns, for many endpoints at once.
+  returns, for many endpoints at once;
+* ``set_cidr_identities``: CIDR prefixes that are identities (``cidr.py``) as a
+  second, native section after the label identities — 24 bytes each instead
+  of their ``GetCIDRLabels`` labels — which every result above then covers.
 
 The results are bit-exact with ``resolve.EndpointSelector.matches`` and
 ``Repository.allows_*_label_access`` / ``get_rules_matching``.  Obtained
@@ -29,6 +32,7 @@ from typing import Iterable, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _native as N
+from . import cidr as CIDR
 from . import resolve as R
 from .classifier import POLICY_KEY_DTYPE
 from .policy import PolicyKey, TrafficDirection, htons
@@ -122,6 +126,31 @@ class ExpandTable:
         return C.byref(self.c)
 
 
+class _IdentityView(Mapping):
+    """The identity cache of both sections as one read-only mapping: the
+    label identities' dicts as given, then each prefix identity's
+    cidr_labels(prefix), built when it is asked for (a /128 has 130 labels;
+    nothing is materialised for a section that is only iterated by key)."""
+
+    def __init__(self, labels: Mapping[int, Mapping[str, str]], prefixes: Mapping[int, "CIDR.Net"]):
+        self._labels, self._prefixes = labels, prefixes
+
+    def __getitem__(self, ident):
+        if ident in self._labels:
+            return self._labels[ident]
+        return CIDR.cidr_labels(self._prefixes[ident])
+
+    def __iter__(self):
+        yield from self._labels
+        yield from self._prefixes
+
+    def __len__(self):
+        return len(self._labels) + len(self._prefixes)
+
+    def __contains__(self, ident):
+        return ident in self._labels or ident in self._prefixes
+
+
 class SelectorCache:
     """The identity cache and a repository's selectors on the device."""
 
@@ -130,9 +159,13 @@ class SelectorCache:
         v = C.c_uint32()
         N.check(N.lib.cg_selcache_create(cl.h, C.byref(v)))
         self.id = v.value
-        self.ids = np.zeros(0, np.uint32)       # identity numbers, in bit order
+        self.ids = np.zeros(0, np.uint32)       # identity numbers of both sections, in bit order
         self.identity_cache: Mapping[int, Mapping[str, str]] = {}
         self._index: dict[int, int] = {}
+        self._label_cache: Mapping[int, Mapping[str, str]] = {}
+        self._label_ids = np.zeros(0, np.uint32)
+        self._cidr_ids = np.zeros(0, np.uint32)
+        self.cidr_identities: dict[int, CIDR.Net] = {}  # the prefix section: {identity: network}
         self.repo: Optional[R.Repository] = None
         self.words = 0
         self._entries_cap = 1 << 16             # entries() starts its buffers here and grows them
@@ -157,10 +190,31 @@ class SelectorCache:
         vb, vo = _strings(vals)
         N.check(N.lib.cg_selcache_set_identities(self.cl.h, self.id, _p(ids) if len(ids) else None, len(ids),
                                                  _p(lab_off), _p(kb), _p(ko), _p(vb), _p(vo)))
-        self.ids = ids
-        self.identity_cache = identity_cache
-        self._index = {int(i): n for n, i in enumerate(ids)}
-        self.words = (len(ids) + 63) // 64
+        self._label_ids, self._label_cache = ids, identity_cache
+        self._sections_changed()
+
+    def set_cidr_identities(self, prefixes: Mapping[int, str]) -> None:
+        """Replace the prefix section ({numeric identity: "prefix"}, e.g.
+        CIDRIdentityAllocator.identities()), all or nothing.  Its bits follow
+        the label identities' in the mapping's order; a prefix identity
+        behaves in every selector as a label identity carrying
+        cidr.cidr_labels(prefix), which is also what identity_cache then
+        returns for it."""
+        nets = [CIDR.to_net(p) for p in prefixes.values()]
+        ids = np.fromiter((int(i) for i in prefixes), np.uint32, len(prefixes))
+        recs = CIDR.nets_to_keys(nets)
+        N.check(N.lib.cg_selcache_set_cidr_identities(self.cl.h, self.id, _p(ids) if len(ids) else None,
+                                                      _p(recs) if len(ids) else None, len(ids)))
+        self._cidr_ids = ids
+        self.cidr_identities = {int(i): n for i, n in zip(ids, nets)}
+        self._sections_changed()
+
+    def _sections_changed(self) -> None:
+        self.ids = np.concatenate([self._label_ids, self._cidr_ids])
+        self.identity_cache = _IdentityView(self._label_cache, self.cidr_identities) if len(self._cidr_ids) \
+            else self._label_cache
+        self._index = {int(i): n for n, i in enumerate(self.ids)}
+        self.words = (len(self.ids) + 63) // 64
 
     @staticmethod
     def compile_repository(repo: R.Repository):
@@ -243,6 +297,10 @@ class SelectorCache:
 
     # ------------------------------------------------------------- reach --
     def _endpoint_indices(self, endpoint_ids: Iterable[int]) -> np.ndarray:
+        endpoint_ids = [int(e) for e in endpoint_ids]
+        for e in endpoint_ids:
+            if e in self.cidr_identities and e not in self._label_cache:
+                raise ValueError(f"identity {e} is a prefix identity ({self.cidr_identities[e]}), not an endpoint")
         try:
             return np.asarray([self._index[int(e)] for e in endpoint_ids], np.uint32)
         except KeyError as ex:

@@ -788,11 +788,27 @@ int cg_selcache_destroy(uint64_t h, uint32_t sc_id);
 int cg_selcache_set_identities(uint64_t h, uint32_t sc_id, const uint32_t* ids, size_t n,
                                const uint32_t* label_off, const uint8_t* key_blob, const uint64_t* key_off,
                                const uint8_t* val_blob, const uint64_t* val_off);
+/* The prefix section, replaced as a whole (all or nothing): identities that
+ * are a CIDR prefix (AllocateCIDRs, pkg/ipcache/cidr.go:26-86).  The cache
+ * then holds the N label identities of cg_selcache_set_identities followed by
+ * these n prefix identities: bits N .. N+n-1 in the given order, no padding
+ * between the sections, words = ceil((N + n) / 64), and every result —
+ * match, reach, expansion, entries, cg_selcache_info — covers both.  Prefix
+ * identity P/m behaves in every selector exactly as a label identity carrying
+ * GetCIDRLabels(P/m) (pkg/labels/cidr/cidr.go:32-50) in that order:
+ * cidr:<P masked to i>/i for i in 0..m when m > 0, then reserved:world, all
+ * with the value "".  Address bits below the prefix are masked (as NewKey
+ * does for the ipcache); a family other than 4 or 6 or a prefix length past
+ * the family's is CG_INVALID_ARGUMENT and keeps the previous tables.
+ * Replacing the label section leaves this one in place and the other way
+ * round; n = 0 (the state after create) leaves a label-only cache. */
+int cg_selcache_set_cidr_identities(uint64_t h, uint32_t sc_id, const uint32_t* ids, const cg_cidr* prefixes,
+                                    size_t n);
 /* The rule set and its selectors, replaced as a whole (all or nothing). */
 int cg_selcache_set_rules(uint64_t h, uint32_t sc_id, const cg_selector_table* sels,
                           const cg_selcache_rules* rules);
-/* sizes of the current tables: identities, words per row (ceil(n / 64)),
- * selectors of the rule set, rules */
+/* sizes of the current tables: identities (both sections), words per row
+ * (ceil(n / 64)), selectors of the rule set, rules */
 int cg_selcache_info(uint64_t h, uint32_t sc_id, size_t* n_identities, size_t* words, size_t* n_selectors,
                      size_t* n_rules);
 /* bits[S][W]: bit i of word w of row s says whether selector s selects

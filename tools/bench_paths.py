@@ -11,6 +11,10 @@ configs, one JSON line each (bench.py covers config 5, the 10K-rule HTTP set):
 * selcache (opt-in, --paths selcache): selector x identity matching and L3
   reach, 65,536 identities, a 10,000-rule repository, 256 endpoints, and the
   expansion of those bitsets into policy-map entries
+* selcache_cidr (opt-in, --paths selcache_cidr): the selector cache's prefix
+  section — 262,144 prefix identities beside 65,536 label identities, the
+  10,000-rule repository plus 1,024 cidr: selectors — against the host walker
+  and against the same prefixes as explicit label identities
 
 Inputs are resident in HBM before timing; kernels are timed with HIP events
 on their stream.  Each line carries the kernel's HBM roofline (algorithmic
@@ -906,6 +910,123 @@ def bench_selcache(torch, dev, stream, cl, args, threads):
     return out
 
 
+def bench_selcache_cidr(torch, dev, stream, cl, args, threads):
+    """The prefix section at the ipcache's scale: 65,536 label identities of
+    8 labels, 262,144 prefix identities (the ipcache bench's /32-heavy mix),
+    the 10,000-rule label repository plus 128 egress rules carrying 1,024
+    distinct cidr: selectors.  Three things, measured in one run:
+    selcache_cidr_match_kernel (a cache holding only the prefix section, so
+    no other kernel runs between the events), the host walker on the same
+    tables, and the same prefix identities as explicit label identities
+    through selcache_match_kernel — what the library could do before the
+    prefix section existed — with that table's device bytes and the host
+    seconds of cg_selcache_set_identities.  The native results are checked
+    against the host walker and, array for array, against the explicit-label
+    cache's before timing."""
+    from cilium_amd import _native as N
+    from cilium_amd import cidr as CIDR
+    from cilium_amd import resolve as R
+    from cilium_amd import synth
+    from cilium_amd.selcache import _strings
+    N_IDS, N_PFX, N_RULES, N_CSEL = 65536, 262144, 10000, 1024
+    cache = synth.identity_cache(N_IDS)
+    keys, _ = synth.ipcache_entries(int(N_PFX * 1.05))
+    keys = keys[:N_PFX]
+    assert len(keys) == N_PFX
+    nets = [CIDR.Net(bytes(k["addr"][:4 if k["family"] == 4 else 16]), int(k["prefixlen"])) for k in keys]
+    prefixes = {200_000 + i: n for i, n in enumerate(nets)}
+    # 1,024 distinct cidr: selectors: ancestors of the prefix identities at mixed lengths
+    rng = np.random.default_rng(0xC1D2)
+    anc: dict[str, None] = {}
+    while len(anc) < N_CSEL:
+        n = nets[int(rng.integers(0, N_PFX))]
+        lo = 8 if n.family == 4 else 32
+        m = int(rng.integers(min(lo, n.ones), n.ones + 1))
+        if m:
+            anc[CIDR.Net(CIDR._mask(n.ip, CIDR.cidr_mask(m, n.bits)), m).text()] = None
+    anc_l = list(anc)
+    repo = synth.label_repository(N_RULES)
+    repo.add_list([R.Rule(R.EndpointSelector.of({"k8s:cidr-bench": str(i)}), [],
+                          [R.EgressRule(ToCIDR=anc_l[8 * i:8 * i + 8])]) for i in range(N_CSEL // 8)])
+    # ---- native: the prefix section alone (the new kernel's own time), then both sections
+    only = cl.selector_cache()
+    only.set_cidr_identities(prefixes)
+    only.set_repository(repo)
+    S, Wc = only.info()["selectors"], only.info()["words"]
+    got = only.match(None)
+    t0 = time.perf_counter()
+    want = only.match(None, diag_cpu=True, threads=threads)
+    walker_s = time.perf_counter() - t0
+    assert np.array_equal(got, want), "selcache cidr match differs from the host walker"
+    d_c = torch.empty(S * Wc, dtype=torch.int64, device=dev)
+    cidr_s = timed(torch, stream, lambda: only.match_dev(None, d_c, stream=stream.cuda_stream), args.steps, 2)
+    assert np.array_equal(d_c.cpu().numpy().view(np.uint64).reshape(S, Wc), want)
+    both = cl.selector_cache()
+    both.set_identities(cache)
+    both.set_cidr_identities(prefixes)
+    both.set_repository(repo)
+    Wb = both.info()["words"]
+    got_b = both.match(None)
+    assert np.array_equal(got_b, both.match(None, diag_cpu=True, threads=threads))
+    assert np.array_equal(got_b[:, N_IDS // 64:], want)  # N_IDS is a multiple of 64: the prefix words are the same
+    d_b = torch.empty(S * Wb, dtype=torch.int64, device=dev)
+    both_s = timed(torch, stream, lambda: both.match_dev(None, d_b, stream=stream.cuda_stream), args.steps, 2)
+    both.destroy()
+    # ---- the same prefix identities as explicit labels
+    t0 = time.perf_counter()
+    ids = np.fromiter(prefixes, np.uint32, N_PFX)
+    lab_off = np.zeros(N_PFX + 1, np.uint32)
+    lkeys: list = []
+    for i, n in enumerate(nets):
+        lkeys.extend(CIDR.cidr_labels(n))
+        lab_off[i + 1] = len(lkeys)
+    kb, ko = _strings(lkeys)
+    vb, vo = _strings([""] * len(lkeys))
+    build_s = time.perf_counter() - t0
+    exp = cl.selector_cache()
+    t0 = time.perf_counter()
+    N.check(N.lib.cg_selcache_set_identities(cl.h, exp.id, N.ptr(ids), N_PFX, N.ptr(lab_off), N.ptr(kb), N.ptr(ko),
+                                             N.ptr(vb), N.ptr(vo)))
+    set_ident_s = time.perf_counter() - t0
+    n_labels = len(lkeys)
+    del lkeys, kb, ko, vb, vo
+    exp.ids, exp.words = ids, Wc
+    exp.set_repository(repo)
+    t0 = time.perf_counter()
+    got_e = exp.match(None)  # the first call publishes: interning the rule set against 9M labels' dictionary, upload
+    publish_s = time.perf_counter() - t0
+    assert np.array_equal(got_e, want), "the explicit-label cache differs from the prefix section"
+    d_e = torch.empty(S * Wc, dtype=torch.int64, device=dev)
+    exp_s = timed(torch, stream, lambda: exp.match_dev(None, d_e, stream=stream.cuda_stream), args.steps, 2)
+    exp.destroy()
+    t0 = time.perf_counter()
+    only.set_cidr_identities(prefixes)
+    only.match(None)
+    native_set_s = time.perf_counter() - t0
+    only.destroy()
+    cells = S * N_PFX
+    native_bytes, explicit_bytes = N_PFX * 24, n_labels * 16 + (N_PFX + 1) * 4
+    return line("selector x prefix-identity cells/s (selcache_cidr_match_kernel: selectors over the prefix section)",
+                cells, cidr_s, (S * Wc * 8 + native_bytes) / cells, "selcache_cidr_match_kernel", cells / walker_s,
+                f"the same tables walked by cg_diag_selcache_match_host on {threads} threads, one full pass", threads,
+                {"unit": "cells/s",
+                 "config": {"workload": "262,144 prefix identities (ipcache mix), 10,000-rule repository + 1,024 cidr: "
+                                        "selectors; 65,536 label identities x 8 labels for the two-section launch",
+                            "prefix_identities": N_PFX, "label_identities": N_IDS, "selectors": S,
+                            "cidr_selectors": N_CSEL},
+                 "native": {"kernel_ms": cidr_s * 1e3, "gcells_per_s": cells / cidr_s / 1e9,
+                            "identity_table_bytes": native_bytes, "host_walker_ms": walker_s * 1e3,
+                            "host_walker_threads": threads, "gpu_over_host_walker": walker_s / cidr_s,
+                            "set_and_publish_s": native_set_s,
+                            "both_sections_kernels_ms": both_s * 1e3},
+                 "explicit_labels": {"kernel": "selcache_match_kernel", "kernel_ms": exp_s * 1e3,
+                                     "labels": n_labels, "identity_table_bytes": explicit_bytes,
+                                     "set_identities_s": set_ident_s, "publish_s": publish_s,
+                                     "python_label_build_s": build_s,
+                                     "explicit_over_native_time": exp_s / cidr_s,
+                                     "explicit_over_native_bytes": explicit_bytes / native_bytes}})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--paths", default="l4,lpm,kafka,ipcache,proxylib,l4ipc")
@@ -924,7 +1045,8 @@ def main():
     fns = {"l4": bench_l4, "lpm": bench_lpm, "kafka": bench_kafka, "ipcache": bench_ipcache,
            "proxylib": bench_proxylib, "l4ipc": bench_l4ipc, "kafkawire": bench_kafka_wire, "httphost": bench_http_host, "httpraw": bench_http_raw,
            "httpfields": bench_http_fields, "memcache": bench_memcache, "cassandra": bench_cassandra,
-           "kafkawirez": lambda *a: bench_kafka_wire(*a, codec_frac=0.5), "selcache": bench_selcache}
+           "kafkawirez": lambda *a: bench_kafka_wire(*a, codec_frac=0.5), "selcache": bench_selcache,
+           "selcache_cidr": bench_selcache_cidr}
     for p in args.paths.split(","):
         print(json.dumps(fns[p](torch, dev, stream, cl, args, threads)), flush=True)
     cl.close()
