@@ -40,6 +40,8 @@ CG_L4_F_CB_POLICY = 0x04
 CG_L4_CAN_ACCESS, CG_L4_INGRESS, CG_L4_EGRESS, CG_L4_IGNORE_DROP = 0, 1, 2, 0x100
 CG_DROP_POLICY = -133
 CG_DROP_FRAG_NOSUPPORT = -157
+CG_DROP_MISSED_TAIL_CALL = -140
+CG_POLICY_ARRAY_SLOTS = 65536
 
 CG_PF_DYN4, CG_PF_DYN6, CG_PF_FIX4, CG_PF_FIX6 = 1, 2, 4, 8
 CG_XDP_DROP, CG_XDP_PASS = 1, 2
@@ -219,6 +221,16 @@ SIGNATURES = {
     "cg_diag_selcache_entries_host": (C.c_int, [_u64, _u32, C.POINTER(SelectorTableC), _p, _sz,
                                                 C.POINTER(ExpandTableC), _p, _p, _p, _sz, _p, _p, _u32]),
     "cg_policymap_sync": (C.c_int, [_u64, _u32, _p, _p, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
+    "cg_policy_array_create": (C.c_int, [_u64, C.POINTER(_u32)]),
+    "cg_policy_array_destroy": (C.c_int, [_u64, _u32]),
+    "cg_policy_array_set": (C.c_int, [_u64, _u32, _p, _p, _sz]),
+    "cg_policy_array_clear": (C.c_int, [_u64, _u32, _p, _sz]),
+    "cg_policy_array_get": (C.c_int, [_u64, _u32, C.c_uint16, C.POINTER(_u32)]),
+    "cg_l4_array_verdicts_dev": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _p]),
+    "cg_l4_array_verdicts_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p]),
+    "cg_l4_array_verdicts_ipcache_dev": (C.c_int, [_u64, _u32, _u32, _u32, C.c_int, _p, _p, _p, _sz, _p, _p]),
+    "cg_l4_array_verdicts_ipcache_host": (C.c_int, [_u64, _u32, _u32, _u32, C.c_int, _p, _p, _p, _sz, _p]),
+    "cg_diag_l4_array_eval_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p]),
 }
 
 

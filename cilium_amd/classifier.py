@@ -4,6 +4,8 @@ Mirrors the reference's entry points for the classification path:
 
 * ``PolicyMap``  — pkg/maps/policymap (Allow/AllowKey/Exists/Delete/DeleteKey/
   DumpToSlice/Flush) + batched ``policy_can_access`` (bpf/lib/policy.h:46-163)
+* ``PolicyArray`` — the policy program array ``cilium_policy[lxc_id]``
+  (bpf/lib/maps.h:44-62): verdicts for a batch addressed to many endpoints
 * ``PreFilter``  — pkg/datapath/prefilter (Insert/Delete/Dump with revisions)
   + batched XDP ``check_filters`` (bpf/bpf_xdp.c:88-184)
 * ``Classifier.update_http_policy`` / ``http_verdicts`` — Envoy
@@ -87,6 +89,10 @@ class Classifier:
     # ------------------------------------------------------------- L4 --
     def policy_map(self, max_entries: int = 0) -> "PolicyMap":
         return PolicyMap(self, max_entries)
+
+    def policy_array(self) -> "PolicyArray":
+        """The policy program array: lxc_id → PolicyMap, verdicts across endpoints."""
+        return PolicyArray(self)
 
     # ------------------------------------------------------------ LPM --
     def prefilter(self, dyn4: bool = False, dyn6: bool = False, fix4: bool = True, fix6: bool = True,
@@ -506,6 +512,13 @@ class PolicyMap:
         N.check(N.lib.cg_policymap_create(cl.h, max_entries, C.byref(v)))
         self.id = v.value
 
+    @classmethod
+    def attach(cls, cl: Classifier, map_id: int) -> "PolicyMap":
+        """The PolicyMap object of an existing map id (PolicyArray.get)."""
+        pm = cls.__new__(cls)
+        pm.cl, pm.id = cl, int(map_id)
+        return pm
+
     @staticmethod
     def _keys(keys: Iterable[PolicyKey]) -> np.ndarray:
         ks = list(keys)
@@ -632,6 +645,99 @@ class PolicyMap:
         tuples = np.ascontiguousarray(tuples, L4_TUPLE_DTYPE)
         out = np.zeros(max(len(tuples), 1), np.int32)
         N.check(N.lib.cg_diag_l4_eval_host(self.cl.h, self.id, _p(tuples), len(tuples), _p(out)))
+        return out[:len(tuples)]
+
+
+class PolicyArray:
+    """The policy program array ``cilium_policy[lxc_id]`` (bpf/lib/maps.h:44-62):
+    slots that name PolicyMaps, and verdicts for tuples that each name their
+    endpoint — one launch for a batch addressed to many endpoints.  A tuple
+    whose slot is empty gets CG_DROP_MISSED_TAIL_CALL (-140) in every mode."""
+
+    def __init__(self, cl: Classifier):
+        self.cl = cl
+        v = C.c_uint32()
+        N.check(N.lib.cg_policy_array_create(cl.h, C.byref(v)))
+        self.id = v.value
+
+    @staticmethod
+    def _lxc(lxc_ids) -> np.ndarray:
+        a = np.asarray(lxc_ids)
+        if a.size and (a.min() < 0 or a.max() >= N.CG_POLICY_ARRAY_SLOTS):
+            raise N.CiliumGPUError(N.CG_INVALID_ARGUMENT, "lxc_id outside the policy array")
+        return np.ascontiguousarray(a, np.uint16).reshape(-1)
+
+    def set(self, lxc_id: int, policy_map: "PolicyMap") -> None:
+        self.set_many([lxc_id], [policy_map])
+
+    def set_many(self, lxc_ids, maps: Sequence) -> None:
+        """All or nothing: an unknown map leaves every slot as it was.
+        maps: PolicyMaps or their ids."""
+        lxc = self._lxc(lxc_ids)
+        ids = np.asarray([getattr(m, "id", m) for m in maps], np.uint32)
+        if len(ids) != len(lxc):
+            raise ValueError("one map per lxc_id")
+        N.check(N.lib.cg_policy_array_set(self.cl.h, self.id, _p(lxc) if len(lxc) else None,
+                                          _p(ids) if len(lxc) else None, len(lxc)))
+
+    def clear(self, lxc_id) -> None:
+        lxc = self._lxc(lxc_id)
+        N.check(N.lib.cg_policy_array_clear(self.cl.h, self.id, _p(lxc) if len(lxc) else None, len(lxc)))
+
+    def get(self, lxc_id: int) -> Optional[int]:
+        """The id of the map in the slot, or None for an empty slot."""
+        lxc = self._lxc(lxc_id)
+        v = C.c_uint32()
+        N.check(N.lib.cg_policy_array_get(self.cl.h, self.id, int(lxc[0]), C.byref(v)))
+        return v.value or None
+
+    def destroy(self) -> None:
+        N.check(N.lib.cg_policy_array_destroy(self.cl.h, self.id))
+
+    def _args(self, lxc_ids, tuples):
+        tuples = np.ascontiguousarray(tuples, L4_TUPLE_DTYPE)
+        lxc = self._lxc(lxc_ids)
+        if len(lxc) != len(tuples):
+            raise ValueError("one lxc_id per tuple")
+        return lxc, tuples, np.zeros(max(len(tuples), 1), np.int32)
+
+    def verdicts(self, lxc_ids, tuples: np.ndarray, mode: int = N.CG_L4_INGRESS) -> np.ndarray:
+        """Tuple i judged by the map in slot lxc_ids[i] as PolicyMap.verdicts
+        judges it with `mode` (the tail-called program is the ingress one)."""
+        lxc, tuples, out = self._args(lxc_ids, tuples)
+        N.check(N.lib.cg_l4_array_verdicts_host(self.cl.h, self.id, mode, _p(lxc), _p(tuples), len(tuples), _p(out)))
+        return out[:len(tuples)]
+
+    def verdicts_via_ipcache(self, ipc: "IPCache", remote: np.ndarray, lxc_ids, tuples: np.ndarray,
+                             mode: int = N.CG_L4_INGRESS) -> np.ndarray:
+        """verdicts with each tuple's identity taken from the ipcache
+        resolution of its remote address (u32 network-order IPv4 addresses,
+        or (n, 16) u8 IPv6 ones, as PolicyMap.verdicts_via_ipcache)."""
+        lxc, tuples, out = self._args(lxc_ids, tuples)
+        if remote.dtype == np.uint8:
+            remote, family = np.ascontiguousarray(remote, np.uint8).reshape(-1, 16), 6
+        else:
+            remote, family = np.ascontiguousarray(remote, np.uint32).reshape(-1), 4
+        if len(remote) != len(tuples):
+            raise ValueError("one remote address per tuple")
+        N.check(N.lib.cg_l4_array_verdicts_ipcache_host(self.cl.h, self.id, ipc.id, mode, family, _p(remote), _p(lxc),
+                                                        _p(tuples), len(tuples), _p(out)))
+        return out[:len(tuples)]
+
+    def verdicts_dev(self, d_lxc_ids, d_tuples, n: int, d_out, stream=None, mode: int = N.CG_L4_INGRESS) -> None:
+        """Device buffers (u16 lxc ids, 12-byte tuples, i32 verdicts), async on `stream`."""
+        N.check(N.lib.cg_l4_array_verdicts_dev(self.cl.h, self.id, mode, _p(d_lxc_ids), _p(d_tuples), n, _p(d_out),
+                                               stream))
+
+    def verdicts_via_ipcache_dev(self, ipc: "IPCache", family: int, d_remote, d_lxc_ids, d_tuples, n: int, d_out,
+                                 stream=None, mode: int = N.CG_L4_INGRESS) -> None:
+        N.check(N.lib.cg_l4_array_verdicts_ipcache_dev(self.cl.h, self.id, ipc.id, mode, family, _p(d_remote),
+                                                       _p(d_lxc_ids), _p(d_tuples), n, _p(d_out), stream))
+
+    def eval_host_diag(self, lxc_ids, tuples: np.ndarray, mode: int = N.CG_L4_INGRESS) -> np.ndarray:
+        """Diagnostics only: the array's tables walked on the CPU as the kernel walks them."""
+        lxc, tuples, out = self._args(lxc_ids, tuples)
+        N.check(N.lib.cg_diag_l4_array_eval_host(self.cl.h, self.id, mode, _p(lxc), _p(tuples), len(tuples), _p(out)))
         return out[:len(tuples)]
 
 

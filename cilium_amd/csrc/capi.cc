@@ -19,6 +19,7 @@
 #include "kafka_wire.h"
 #include "kernels.h"
 #include "l4.h"
+#include "l4_array.h"
 #include "l4_walk.h"
 #include "ipcache.h"
 #include "lpm.h"
@@ -72,6 +73,12 @@ int guarded(F&& f) {
 PolicyMapState& get_map(Engine& e, uint32_t id) {
   auto it = e.maps.find(id);
   if (it == e.maps.end()) fail(CG_NOT_FOUND, "unknown policy map id");
+  return *it->second;
+}
+
+PolicyArrayState& get_arr(Engine& e, uint32_t id) {
+  auto it = e.arrays.find(id);
+  if (it == e.arrays.end()) fail(CG_NOT_FOUND, "unknown policy array id");
   return *it->second;
 }
 
@@ -185,6 +192,7 @@ void cg_close(uint64_t h) {
       if (r) r->close();
     }
     (void)hipStreamSynchronize((hipStream_t)e->stream);
+    e->arrays.clear();
     e->maps.clear();
     e->prefilters.clear();
     e->ipcaches.clear();
@@ -225,6 +233,7 @@ int cg_policymap_destroy(uint64_t h, uint32_t map_id) {
     get_map(*e, map_id);
     if (e->has_gpu()) dev_sync(*e, nullptr);
     e->maps.erase(map_id);
+    for (auto& arr : e->arrays) arr.second->drop_map(map_id);  // its slots are empty from now on
   });
 }
 
@@ -533,6 +542,172 @@ int cg_l4_verdicts_ipcache6_dev(uint64_t h, uint32_t map_id, uint32_t ipc_id, co
 int cg_l4_verdicts_ipcache6_host(uint64_t h, uint32_t map_id, uint32_t ipc_id, const uint8_t* remote_v6,
                                  const cg_l4_tuple* tuples, size_t n, int32_t* verdicts) {
   return guarded([&] { l4_ipc_host(*get(h), map_id, ipc_id, 6, remote_v6, tuples, n, verdicts); });
+}
+
+// ----------------------------------------------- policy program array ----
+// cilium_policy[lxc_id] (bpf/lib/maps.h:44-62): slots naming policy maps, and
+// verdict entries that take each tuple's lxc_id (l4_array.h, kernels_l4_array.hip).
+int cg_policy_array_create(uint64_t h, uint32_t* arr_id) {
+  return guarded([&] {
+    auto e = get(h);
+    if (!arr_id) fail(CG_INVALID_ARGUMENT, "arr_id is NULL");
+    std::lock_guard<std::mutex> lk(e->mu);
+    const uint32_t id = e->next_id++;
+    e->arrays[id] = std::make_unique<PolicyArrayState>();
+    *arr_id = id;
+  });
+}
+
+int cg_policy_array_destroy(uint64_t h, uint32_t arr_id) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    get_arr(*e, arr_id);
+    if (e->has_gpu()) dev_sync(*e, nullptr);
+    e->arrays.erase(arr_id);
+  });
+}
+
+int cg_policy_array_set(uint64_t h, uint32_t arr_id, const uint16_t* lxc_ids, const uint32_t* map_ids, size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    PolicyArrayState& a = get_arr(*e, arr_id);
+    if (n && (!lxc_ids || !map_ids)) fail(CG_INVALID_ARGUMENT, "NULL lxc_ids/map_ids");
+    for (size_t i = 0; i < n; ++i) get_map(*e, map_ids[i]);  // all checked before any slot changes
+    for (size_t i = 0; i < n; ++i) a.put(lxc_ids[i], map_ids[i]);
+  });
+}
+
+int cg_policy_array_clear(uint64_t h, uint32_t arr_id, const uint16_t* lxc_ids, size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    PolicyArrayState& a = get_arr(*e, arr_id);
+    if (n && !lxc_ids) fail(CG_INVALID_ARGUMENT, "NULL lxc_ids");
+    for (size_t i = 0; i < n; ++i) a.put(lxc_ids[i], 0);
+  });
+}
+
+int cg_policy_array_get(uint64_t h, uint32_t arr_id, uint16_t lxc_id, uint32_t* map_id) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    PolicyArrayState& a = get_arr(*e, arr_id);
+    if (!map_id) fail(CG_INVALID_ARGUMENT, "map_id is NULL");
+    *map_id = a.slot_map[lxc_id];
+  });
+}
+
+// One snapshot of the whole array, taken under the handle lock: dirty members
+// are rebuilt, and the slot words and records are uploaded again only if a
+// slot or a member's published tables changed since the last upload.  The
+// holder keeps every member's tables and counters alive (l4_array.h).
+struct L4ArrView {
+  std::shared_ptr<L4ArrTables> keep;
+  L4ArrDev dev;
+};
+static L4ArrView l4_array_view(Engine& e, uint32_t arr_id) {
+  std::lock_guard<std::mutex> lk(e.mu);
+  PolicyArrayState& a = get_arr(e, arr_id);
+  std::vector<std::shared_ptr<DevTables>> members;
+  std::vector<L4Dev> recs;
+  bool changed = a.slots_changed || !a.tab;
+  for (const auto& ref : a.refs) {
+    PolicyMapState& m = get_map(e, ref.first);  // a destroyed map has left refs (cg_policymap_destroy)
+    if (m.dirty) m.rebuild(e);
+    if (!changed && a.tab->members[members.size()] != m.tab) changed = true;
+    members.push_back(m.tab);
+    recs.push_back(m.dev);
+  }
+  if (changed) {
+    std::map<uint32_t, uint32_t> word;  // map id -> 1 + record index
+    for (const auto& ref : a.refs) word.emplace(ref.first, (uint32_t)word.size() + 1);
+    std::vector<uint32_t> slot(CG_POLICY_ARRAY_SLOTS, 0u);
+    for (uint32_t s = 0; s < CG_POLICY_ARRAY_SLOTS; ++s)
+      if (a.slot_map[s]) slot[s] = word[a.slot_map[s]];
+    if (recs.empty()) recs.push_back(L4Dev{});  // never read: every slot word is 0
+    e.set_device();
+    auto t = std::make_shared<L4ArrTables>();
+    t->members = std::move(members);
+    L4ArrDev d{};
+    d.slot = t->own.add(slot);
+    d.recs = t->own.add(recs);
+    a.tab = std::move(t);  // publish
+    a.dev = d;
+    a.slots_changed = false;
+  }
+  return {a.tab, a.dev};
+}
+
+static void l4_array_dev(Engine& e, uint32_t arr_id, const IpcView* iv, uint32_t mode, int family, const void* d_addr,
+                         const uint16_t* d_lxc, const cg_l4_tuple* d_t, size_t n, int32_t* d_out, void* s) {
+  e.require_gpu();
+  const L4ArrView v = l4_array_view(e, arr_id);
+  e.set_device();
+  check_launch(launch_l4_array(v.dev, iv ? iv->dev : IpcacheDev{}, family, d_addr, d_lxc, d_t, n, d_out, mode,
+                               stream_of(e, s), e.cus),
+               "l4 array kernel launch");
+  v.keep->own.fence.record(stream_of(e, s));
+  if (iv) fence(iv->keep, stream_of(e, s));
+}
+
+static void l4_array_host(Engine& e, uint32_t arr_id, const IpcView* iv, uint32_t mode, int family, const void* addr,
+                          const uint16_t* lxc, const cg_l4_tuple* t, size_t n, int32_t* out) {
+  e.require_gpu();
+  if (n && (!lxc || !t || !out || (family && !addr))) fail(CG_INVALID_ARGUMENT, "NULL lxc_ids/tuples/verdicts");
+  const L4ArrView v = l4_array_view(e, arr_id);
+  std::vector<HostIn> ins = {{lxc, sizeof(uint16_t)}, {t, sizeof(cg_l4_tuple)}};
+  if (family) ins.push_back({addr, family == 6 ? 16u : 4u});
+  host_pipeline(e, n, ins, {{out, sizeof(int32_t)}}, [&](void* const* din, void* const* dout, size_t cnt, void* st) {
+    check_launch(launch_l4_array(v.dev, iv ? iv->dev : IpcacheDev{}, family, family ? din[2] : nullptr,
+                                 (const uint16_t*)din[0], din[1], cnt, (int32_t*)dout[0], mode, st, e.cus),
+                 "l4 array kernel launch");
+  });
+}
+
+static void check_family(int family) {
+  if (family != 4 && family != 6) fail(CG_INVALID_ARGUMENT, "family must be 4 or 6");
+}
+
+int cg_l4_array_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint16_t* d_lxc_ids,
+                             const cg_l4_tuple* d_tuples, size_t n, int32_t* d_verdicts, void* stream) {
+  return guarded([&] {
+    l4_array_dev(*get(h), arr_id, nullptr, check_l4_mode(mode), 0, nullptr, d_lxc_ids, d_tuples, n, d_verdicts, stream);
+  });
+}
+
+int cg_l4_array_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint16_t* lxc_ids,
+                              const cg_l4_tuple* tuples, size_t n, int32_t* verdicts) {
+  return guarded([&] {
+    l4_array_host(*get(h), arr_id, nullptr, check_l4_mode(mode), 0, nullptr, lxc_ids, tuples, n, verdicts);
+  });
+}
+
+int cg_l4_array_verdicts_ipcache_dev(uint64_t h, uint32_t arr_id, uint32_t ipc_id, uint32_t mode, int family,
+                                     const void* d_remote, const uint16_t* d_lxc_ids, const cg_l4_tuple* d_tuples,
+                                     size_t n, int32_t* d_verdicts, void* stream) {
+  return guarded([&] {
+    auto e = get(h);
+    check_l4_mode(mode);
+    check_family(family);
+    e->require_gpu();
+    const IpcView iv = ipc_view(*e, ipc_id);
+    l4_array_dev(*e, arr_id, &iv, mode, family, d_remote, d_lxc_ids, d_tuples, n, d_verdicts, stream);
+  });
+}
+
+int cg_l4_array_verdicts_ipcache_host(uint64_t h, uint32_t arr_id, uint32_t ipc_id, uint32_t mode, int family,
+                                      const void* remote, const uint16_t* lxc_ids, const cg_l4_tuple* tuples, size_t n,
+                                      int32_t* verdicts) {
+  return guarded([&] {
+    auto e = get(h);
+    check_l4_mode(mode);
+    check_family(family);
+    e->require_gpu();
+    const IpcView iv = ipc_view(*e, ipc_id);
+    l4_array_host(*e, arr_id, &iv, mode, family, remote, lxc_ids, tuples, n, verdicts);
+  });
 }
 
 // ----------------------------------------------------------------- LPM ----
@@ -2281,6 +2456,40 @@ int cg_diag_l4_eval_host(uint64_t h, uint32_t map_id, const cg_l4_tuple* t, size
       const int which = l4_resolve(T, [&](uint32_t b) { return T.fp[b]; }, w[0], w1,
                                    (w1 >> 24) & CG_L4_F_FRAGMENT, &val);
       out[i] = l4_wrap(l4_verdict(which, val, w1 >> 24), CG_L4_CAN_ACCESS);
+    }
+  });
+}
+
+// Per tuple as l4_array_kernel does it: the slot's map, then l4_kernel's walk
+// with `mode`; an empty slot is the missed tail call.
+int cg_diag_l4_array_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint16_t* lxc, const cg_l4_tuple* t,
+                               size_t n, int32_t* out) {
+  return guarded([&] {
+    auto e = get(h);
+    check_l4_mode(mode);
+    std::lock_guard<std::mutex> lk(e->mu);
+    PolicyArrayState& a = get_arr(*e, arr_id);
+    if (n && (!lxc || !t || !out)) fail(CG_INVALID_ARGUMENT, "NULL lxc_ids/tuples/verdicts");
+    std::map<uint32_t, L4Dev> views;
+    for (const auto& ref : a.refs) {
+      PolicyMapState& m = get_map(*e, ref.first);
+      if (m.dirty) m.rebuild(*e);
+      views.emplace(ref.first, m.host_view());
+    }
+    for (size_t i = 0; i < n; ++i) {
+      const uint32_t map_id = a.slot_map[lxc[i]];
+      if (!map_id) {
+        out[i] = CG_DROP_MISSED_TAIL_CALL;
+        continue;
+      }
+      const L4Dev& T = views.find(map_id)->second;
+      uint32_t w[3];  // identity, dport | proto << 16 | flags << 24, len
+      memcpy(w, &t[i], sizeof(w));
+      const uint32_t w1 = l4_mode_word(w[1], mode);
+      uint32_t val = 0;
+      const int which = l4_resolve(T, [&](uint32_t b) { return T.fp[b]; }, w[0], w1,
+                                   (w1 >> 24) & CG_L4_F_FRAGMENT, &val);
+      out[i] = l4_wrap(l4_verdict(which, val, w1 >> 24), mode);
     }
   });
 }

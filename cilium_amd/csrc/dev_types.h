@@ -104,6 +104,17 @@ CG_HD inline void l4_place(uint64_t key, uint32_t mask, uint32_t* b1, uint32_t* 
   l4_place_h(l4_h(key), mask, b1, b2, fp);
 }
 
+// The policy program array (cilium_policy[lxc_id], bpf/lib/maps.h:44-62) as
+// the array kernel reads it: one word per slot, 0 for an empty slot, else
+// 1 + the index of the member map's record; a record is that map's L4Dev
+// (32 bytes, two 16-byte loads), so a map that sits in several slots has one
+// record and one set of counters.
+struct L4ArrDev {
+  const uint32_t* slot;  // CG_POLICY_ARRAY_SLOTS words
+  const L4Dev* recs;     // one per member map
+};
+static_assert(sizeof(L4Dev) == 32, "the array kernel reads a record as two 16-byte loads");
+
 // ----------------------------------------------------------------- LPM ----
 // IPv4: two levels of 2-bit codes (0 not covered, 1 covered, 2 mixed/partial),
 // 16 per u32 word.  Level 1: one code per /16 (16 KiB, cache resident).
@@ -908,6 +919,18 @@ CG_HD inline uint64_t ipc_v6_search_value(const IpcacheDev& t, uint64_t hi, uint
     l = l < r ? l : r;
   }
   return t.runs6[4 * (size_t)ipc_v6_run(t, hi, lo, l, r) + 2];
+}
+
+// The remote identity of the egress flow (bpf_lxc.c:205-215 v6, :509-518 v4):
+// lookup_ip{4,6}_remote_endpoint resolved to sec_label, or WORLD_ID on a miss
+// or a zero sec_label (the tables store that resolution).  en: the set
+// bucket's entry, kr / v: its last run's key and value.
+CG_HDI uint32_t ipc_v6_identity(const IpcacheDev& ipc, uint64_t hi, uint64_t lo, uint4 en, uint4 kr, uint32_t v) {
+  uint64_t xv;
+  if (en.w && ipc_ex6_find(ipc, hi, lo, ipc_ex6_hash(hi, lo) & ipc.ex6_mask, &xv)) return (uint32_t)xv;  // a /128
+  if (!le128(((uint64_t)kr.y << 32) | kr.x, ((uint64_t)kr.w << 32) | kr.z, hi, lo))
+    v = (uint32_t)ipc_v6_search_value(ipc, hi, lo, en.x, en.y, en.z);
+  return v;
 }
 
 // ------------------------------------------------------- selector cache ----

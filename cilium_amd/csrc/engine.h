@@ -156,6 +156,7 @@ class StagingPool {
 };
 
 struct PolicyMapState;
+struct PolicyArrayState;
 struct PrefilterState;
 struct IpcacheState;
 struct SelcacheState;
@@ -172,6 +173,7 @@ struct Engine {
   std::mutex mu;  // control-plane updates and map state
   uint32_t next_id = 1;
   std::map<uint32_t, std::unique_ptr<PolicyMapState>> maps;
+  std::map<uint32_t, std::unique_ptr<PolicyArrayState>> arrays;  // policy program arrays (l4_array.h)
   std::map<uint32_t, std::unique_ptr<PrefilterState>> prefilters;
   std::map<uint32_t, std::unique_ptr<IpcacheState>> ipcaches;
   std::map<uint32_t, std::unique_ptr<SelcacheState>> selcaches;

@@ -16,6 +16,12 @@ int launch_l4(const L4Dev& t, const void* tuples, size_t n, int32_t* out, uint32
 // addrs[i] (remote address, network order: u32 for family 4, 16 bytes for 6).
 int launch_l4_ipcache(const L4Dev& t, const IpcacheDev& ipc, int family, const void* addrs, const void* tuples,
                       size_t n, int32_t* out, uint32_t mode, void* stream, int cus);
+// The policy program array (kernels_l4_array.hip): tuple i is judged by the
+// map in slot lxc[i] of A, CG_DROP_MISSED_TAIL_CALL for an empty slot.
+// family 0: the tuple's own identity; 4 / 6: the ipcache resolution of
+// addrs[i], as launch_l4_ipcache.
+int launch_l4_array(const L4ArrDev& A, const IpcacheDev& ipc, int family, const void* addrs, const uint16_t* lxc,
+                    const void* tuples, size_t n, int32_t* out, uint32_t mode, void* stream, int cus);
 int launch_lpm(const LpmDev& t, bool v4_filter, bool v6_filter, const uint32_t* v4, size_t n4,
                uint8_t* out4, const uint8_t* v6, size_t n6, uint8_t* out6, void* stream, int cus);
 // order (optional): out[order[slot]] instead of out[slot] (request order;

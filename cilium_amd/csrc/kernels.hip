@@ -59,18 +59,6 @@ __device__ void l4_flush(const L4Dev& t, unsigned long long* lcnt) {
   __syncthreads();
 }
 
-// The remote identity of the egress flow (bpf_lxc.c:205-215 v6, :509-518 v4):
-// lookup_ip{4,6}_remote_endpoint resolved to sec_label, or WORLD_ID on a miss
-// or a zero sec_label (the tables store that resolution, dev_types.h).
-__device__ __forceinline__ uint32_t ipc_v6_identity(const IpcacheDev& ipc, uint64_t hi, uint64_t lo, uint4 en,
-                                                    uint4 kr, uint32_t v) {
-  uint64_t xv;
-  if (en.w && ipc_ex6_find(ipc, hi, lo, ipc_ex6_hash(hi, lo) & ipc.ex6_mask, &xv)) return (uint32_t)xv;  // a /128
-  if (!le128(((uint64_t)kr.y << 32) | kr.x, ((uint64_t)kr.w << 32) | kr.z, hi, lo))
-    v = (uint32_t)ipc_v6_search_value(ipc, hi, lo, en.x, en.y, en.z);
-  return v;
-}
-
 // Tables whose fingerprints and counters fit LDS together (max_entries*8 +
 // nbuckets*4 <= 160 KiB; the 16,384-entry default): per tuple three key
 // hashes, six LDS fingerprint reads, and a slot read only on a fingerprint

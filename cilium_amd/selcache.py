@@ -491,6 +491,31 @@ class SelectorCache:
         ents = self.endpoint_policy_map_entries(endpoint_ids, redirect_ports)
         return [pm.sync(k, p) for pm, (k, p) in zip(maps, ents)]
 
+    def sync_policy_array(self, endpoint_ids: Iterable[int], lxc_ids: Iterable[int], array,
+                          redirect_ports: Optional[Mapping[tuple, int]] = None,
+                          diag_cpu: bool = False) -> list[tuple[int, int]]:
+        """sync_policy_maps over the maps in slots lxc_ids[i] of `array` (a
+        PolicyArray): endpoint i's desired state goes into the map its slot
+        names; an empty slot gets a fresh PolicyMap, set into the slot.
+        Returns the (added, deleted) counts per endpoint.  diag_cpu: the
+        entries come from the host evaluator (diagnostics, no GPU needed)."""
+        from .classifier import PolicyMap
+        endpoint_ids, lxc_ids = list(endpoint_ids), [int(x) for x in lxc_ids]
+        if len(lxc_ids) != len(endpoint_ids):
+            raise ValueError("one lxc_id per endpoint")
+        maps = []
+        for lxc in lxc_ids:
+            map_id = array.get(lxc)
+            if map_id is None:
+                maps.append(PolicyMap(self.cl))
+                array.set(lxc, maps[-1])
+            else:
+                maps.append(PolicyMap.attach(self.cl, map_id))
+        if not diag_cpu:
+            return self.sync_policy_maps(endpoint_ids, maps, redirect_ports)
+        ents = self.endpoint_policy_map_entries(endpoint_ids, redirect_ports, diag_cpu=True)
+        return [pm.sync(k, p) for pm, (k, p) in zip(maps, ents)]
+
     def endpoint_policy_map_states(self, endpoint_ids: Iterable[int],
                                    redirect_ports: Optional[Mapping[tuple, int]] = None,
                                    diag_cpu: bool = False) -> list[dict]:

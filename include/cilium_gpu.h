@@ -173,6 +173,54 @@ int cg_l4_policy_verdicts_dev(uint64_t h, uint32_t map_id, uint32_t mode, const 
 int cg_l4_policy_verdicts_host(uint64_t h, uint32_t map_id, uint32_t mode, const cg_l4_tuple* tuples,
                                size_t n, int32_t* verdicts);
 
+/* The policy program array, cilium_policy[lxc_id] (bpf/lib/maps.h:44-62):
+ * delivery to a local endpoint tail-calls into that endpoint's own policy
+ * program, tail_call(skb, &cilium_policy, ep->lxc_id) (bpf/lib/l3.h:99,130),
+ * which runs policy_can_access_ingress on the endpoint's map (bpf_lxc.c:948).
+ * Here a slot names a policy map, and the cg_l4_array_verdicts_* entries take
+ * each tuple's lxc_id, so one launch judges a batch addressed to many
+ * endpoints.
+ *  - set and clear are all-or-nothing per call: every argument is checked
+ *    before any slot changes.
+ *  - A tuple that names an empty slot gets CG_DROP_MISSED_TAIL_CALL in every
+ *    mode, CG_L4_IGNORE_DROP included, and moves no counter: the tail call
+ *    missed, so nothing of policy.h ran (l3.h:99-100).
+ *  - Destroying a policy map empties the slots that name it.  Its tables stay
+ *    alive until the launches already enqueued have run.
+ *  - A verdict call sees one snapshot of the whole array, taken under the
+ *    handle lock: a concurrent cg_policymap_* or cg_policy_array_* update is
+ *    seen by that call entirely or not at all. */
+#define CG_DROP_MISSED_TAIL_CALL (-140) /* bpf/lib/common.h:247 */
+#define CG_POLICY_ARRAY_SLOTS 65536u    /* POLICY_PROG_MAP_SIZE, node_config.h:62 */
+int cg_policy_array_create(uint64_t h, uint32_t* arr_id);
+int cg_policy_array_destroy(uint64_t h, uint32_t arr_id);
+/* slot lxc_ids[i] -> map_ids[i].  CG_NOT_FOUND for an unknown map (nothing
+ * applied); an lxc_id >= CG_POLICY_ARRAY_SLOTS would be CG_INVALID_ARGUMENT,
+ * which a uint16_t cannot reach.  The same map may sit in several slots. */
+int cg_policy_array_set(uint64_t h, uint32_t arr_id, const uint16_t* lxc_ids, const uint32_t* map_ids, size_t n);
+int cg_policy_array_clear(uint64_t h, uint32_t arr_id, const uint16_t* lxc_ids, size_t n);
+/* *map_id = 0 for an empty slot. */
+int cg_policy_array_get(uint64_t h, uint32_t arr_id, uint16_t lxc_id, uint32_t* map_id);
+
+/* Verdicts across endpoints: tuple i is judged by the map in slot lxc_ids[i],
+ * with `mode` as cg_l4_policy_verdicts_* take it.  The verdict is bit for bit
+ * what cg_l4_policy_verdicts_* return for that tuple on that map, and the
+ * matching entry's packets and bytes advance exactly as there.  18 bytes per
+ * tuple: 12 of cg_l4_tuple, 2 of lxc_id, 4 of verdict. */
+int cg_l4_array_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint16_t* d_lxc_ids,
+                             const cg_l4_tuple* d_tuples, size_t n, int32_t* d_verdicts, void* stream);
+int cg_l4_array_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint16_t* lxc_ids,
+                              const cg_l4_tuple* tuples, size_t n, int32_t* verdicts);
+/* The same with each tuple's identity taken from the ipcache resolution of
+ * its remote address, as cg_l4_verdicts_ipcache*_ resolve it (family 4: u32
+ * addresses in network order; 6: 16 bytes each), then `mode`. */
+int cg_l4_array_verdicts_ipcache_dev(uint64_t h, uint32_t arr_id, uint32_t ipc_id, uint32_t mode, int family,
+                                     const void* d_remote, const uint16_t* d_lxc_ids, const cg_l4_tuple* d_tuples,
+                                     size_t n, int32_t* d_verdicts, void* stream);
+int cg_l4_array_verdicts_ipcache_host(uint64_t h, uint32_t arr_id, uint32_t ipc_id, uint32_t mode, int family,
+                                      const void* remote, const uint16_t* lxc_ids, const cg_l4_tuple* tuples,
+                                      size_t n, int32_t* verdicts);
+
 /* ======================================================================== */
 /* LPM: XDP CIDR prefilter — bpf/bpf_xdp.c:88-184,                           */
 /* pkg/datapath/prefilter/prefilter.go:57-298                                */
@@ -913,6 +961,10 @@ int cg_diag_kafka_decode_host(uint64_t h, const uint8_t* raw, const uint64_t* ra
                               uint32_t* arena, size_t arena_cap, size_t* arena_used, uint8_t* status);
 int cg_diag_l4_eval_host(uint64_t h, uint32_t map_id, const cg_l4_tuple* tuples, size_t n,
                          int32_t* verdicts);
+/* The array's tables walked on the host exactly as l4_array_kernel walks
+ * them, with `mode` applied (no counters). */
+int cg_diag_l4_array_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint16_t* lxc_ids,
+                               const cg_l4_tuple* tuples, size_t n, int32_t* verdicts);
 /* The ipcache tables walked on the host exactly as ipcache_kernel does. */
 int cg_diag_ipcache_eval_host(uint64_t h, uint32_t ipc_id, const uint32_t* v4, size_t n4,
                               cg_remote_endpoint_info* out4, const uint8_t* v6, size_t n6,

@@ -15,6 +15,10 @@ configs, one JSON line each (bench.py covers config 5, the 10K-rule HTTP set):
   section — 262,144 prefix identities beside 65,536 label identities, the
   10,000-rule repository plus 1,024 cidr: selectors — against the host walker
   and against the same prefixes as explicit label identities
+* l4_array (opt-in, --paths l4_array): the policy program array — 256 maps of
+  config 2's table mix, 100M tuples that each name their endpoint, against
+  the per-map route (pre-grouped launches; sort + launches + scatter from
+  host data) and the single-map figure
 
 Inputs are resident in HBM before timing; kernels are timed with HIP events
 on their stream.  Each line carries the kernel's HBM roofline (algorithmic
@@ -136,6 +140,150 @@ def bench_l4(torch, dev, stream, cl, args, threads):
                 if cpu else "", threads,
                 {"config": {"workload": "BASELINE config 2: 16,384-entry policy map, 100M tuples",
                             "entries": int(len(keys)), "tuples": n}})
+
+
+def _l4_table_mix(rng, n_entries=16384, n_ids=16384):
+    """synth.l4_table's mix (70% {id,port,proto,dir}, 20% {id,0,0,dir}, 10%
+    {0,port,proto,dir}; 20% of the entries redirect) drawn with array
+    operations, so that 256 tables take seconds."""
+    from cilium_amd.classifier import POLICY_KEY_DTYPE
+    m = n_entries * 5 // 4
+    ids = np.concatenate([np.arange(1, 6), 256 + np.arange(n_ids)]).astype(np.uint32)
+    r = rng.random(m)
+    k = np.zeros(m, POLICY_KEY_DTYPE)
+    port = rng.integers(1, 65536, m).astype(np.uint16)
+    k["sec_label"] = np.where(r < 0.9, ids[rng.integers(0, len(ids), m)], 0)
+    k["dport"] = np.where((r < 0.7) | (r >= 0.9), (port & 0xFF) << 8 | port >> 8, 0)
+    k["protocol"] = np.where(k["dport"] != 0, np.where(rng.random(m) < 0.5, 6, 17), 0)
+    k["egress"] = rng.integers(0, 2, m)
+    _, first = np.unique(k.view(np.uint64), return_index=True)
+    k = k[np.sort(first)[:n_entries]]
+    assert len(k) == n_entries
+    p = np.where(rng.random(n_entries) < 0.8, 0, rng.integers(10000, 11000, n_entries)).astype(np.uint16)
+    return k, ((p & 0xFF) << 8 | p >> 8).astype(np.uint16)
+
+
+def _l4_array_tuples(rng, lxc_map, tports, n_ids=16384):
+    """synth.l4_tuples' recipe with each tuple's table ports taken from its
+    own endpoint's table (tports[map]): identity uniform over the ids + 10
+    unknown, dport 50% a table port (Zipf s=1.1) / 50% uniform, proto and dir
+    50/50, fragment 1%, CB_POLICY 1%, len 64-1500."""
+    from cilium_amd.classifier import L4_TUPLE_DTYPE
+    n = len(lxc_map)
+    t = np.zeros(n, L4_TUPLE_DTYPE)
+    ids = np.concatenate([np.arange(1, 6), 256 + np.arange(n_ids), 900000 + np.arange(10)]).astype(np.uint32)
+    t["identity"] = ids[rng.integers(0, len(ids), n)]
+    z = np.minimum(rng.zipf(1.1, n) - 1, tports.shape[1] - 1)
+    uni = rng.integers(1, 65536, n).astype(np.uint16)
+    t["dport"] = np.where(rng.random(n) < 0.5, tports[lxc_map, z], (uni & 0xFF) << 8 | uni >> 8)
+    t["proto"] = np.where(rng.random(n) < 0.5, 6, 17)
+    t["flags"] = ((rng.random(n) < 0.5).astype(np.uint8) | (rng.random(n) < 0.01).astype(np.uint8) << 1 |
+                  (rng.random(n) < 0.01).astype(np.uint8) << 2)
+    t["len"] = rng.integers(64, 1501, n)
+    return t
+
+
+def bench_l4_array(torch, dev, stream, cl, args, threads):
+    """The policy program array: 256 endpoints' maps (config 2's table mix,
+    each drawn with its own seed), config 2's tuples tiled to 100M, every
+    tuple naming its endpoint — uniformly per tuple, or in runs of geometric
+    length (mean 64).  Checked against cg_diag_l4_array_eval_host before
+    timing.  Beside the array kernel: the per-map route in the same process
+    (the tuples pre-grouped by endpoint, 256 cg_l4_policy_verdicts_dev
+    launches; and its wall time from ungrouped host data, with the host
+    argsort and the scatter back), and bench_l4's single-map figure."""
+    from cilium_amd import _native as N
+    E, D = 256, args.array_tuples
+    n = min(100_000_000, 2 * D)  # the first copy and the start of a second
+    mode = N.CG_L4_INGRESS
+    rng = np.random.default_rng(0xA77A)
+    maps, tports = [], []
+    for e in range(E):
+        keys, ports = _l4_table_mix(np.random.default_rng(1000 + e))
+        pm = cl.policy_map()
+        pm.allow_keys(keys, ports)
+        maps.append(pm)
+        tports.append(keys["dport"][keys["dport"] != 0])
+    tports = np.stack([p[:min(len(q) for q in tports)] for p in tports])
+    slots = (np.arange(E) * 257).astype(np.uint16)  # 0, 257, ..., 65535
+    arr = cl.policy_array()
+    arr.set_many(slots, maps)
+    runs = rng.geometric(1.0 / 64, D // 32)
+    mixes = {"uniform": rng.integers(0, E, D).astype(np.uint16),
+             "runs64": np.repeat(rng.integers(0, E, len(runs)).astype(np.uint16), runs)[:D]}
+    assert len(mixes["runs64"]) == D
+    d_o = torch.empty(n, dtype=torch.int32, device=dev)
+    res, cpu = {}, None
+    for name, which in mixes.items():
+        tup = _l4_array_tuples(rng, which, tports)
+        lxc = slots[which]
+        d_t = torch.empty(n * 12, dtype=torch.uint8, device=dev)
+        d_t[:D * 12].copy_(torch.from_numpy(tup.view(np.uint8)))
+        d_t[D * 12:].copy_(d_t[:(n - D) * 12])
+        d_l = torch.empty(n, dtype=torch.int16, device=dev)
+        d_l[:D].copy_(torch.from_numpy(lxc.view(np.int16)))
+        d_l[D:].copy_(d_l[:n - D])
+        # the check: the first copy against the host evaluator
+        arr.verdicts_dev(d_l, d_t, D, d_o, stream=stream.cuda_stream, mode=mode)
+        stream.synchronize()
+        t0 = time.perf_counter()
+        want = arr.eval_host_diag(lxc, tup, mode)
+        cpu = cpu or D / (time.perf_counter() - t0)
+        assert np.array_equal(d_o[:D].cpu().numpy(), want), "array verdicts differ from the host evaluator"
+        sec = timed(torch, stream,
+                    lambda: arr.verdicts_dev(d_l, d_t, n, d_o, stream=stream.cuda_stream, mode=mode), args.steps, 2)
+        r = res[name] = {"kernel_ms": sec * 1e3, "Gtuples_s": n / sec / 1e9,
+                         "roofline_frac": n * 18 / sec / 1e9 / HBM_PEAK_GBPS,
+                         "hit_frac": float((want >= 0).mean())}
+        # the per-map route, kernels only: grouped on the device beforehand
+        order = torch.argsort(d_l.to(torch.int32) & 0xFFFF, stable=True)
+        g_t = d_t.view(n, 12)[order].contiguous()
+        counts = np.bincount(which, minlength=E).astype(np.int64) * (n // D)
+        counts += np.bincount(which[:n - D * (n // D)], minlength=E)
+        del order
+        offs = np.concatenate([[0], np.cumsum(counts)])
+        g_o = torch.empty(n, dtype=torch.int32, device=dev)
+
+        def per_map(g_t=g_t, g_o=g_o, offs=offs):
+            for e in range(E):
+                a, b = int(offs[e]), int(offs[e + 1])
+                maps[e].verdicts_dev(g_t[a:b], b - a, g_o[a:b], stream=stream.cuda_stream, mode=mode)
+        sec_pm = timed(torch, stream, per_map, args.steps, 1)
+        r["per_map_grouped"] = {"kernel_ms": sec_pm * 1e3, "Gtuples_s": n / sec_pm / 1e9, "launches": E}
+        del g_t, g_o
+        # the per-map route from ungrouped host data: what a caller of the
+        # single-map entries has to do (sort, 256 calls, scatter back)
+        t0 = time.perf_counter()
+        h_order = np.argsort(lxc, kind="stable")
+        h_t = tup[h_order]
+        h_offs = np.concatenate([[0], np.cumsum(np.bincount(which, minlength=E))])
+        dd_t = torch.from_numpy(h_t.view(np.uint8)).to(dev)
+        dd_o = torch.empty(D, dtype=torch.int32, device=dev)
+        for e in range(E):
+            a, b = int(h_offs[e]), int(h_offs[e + 1])
+            maps[e].verdicts_dev(dd_t[a * 12:b * 12], b - a, dd_o[a:b], stream=stream.cuda_stream, mode=mode)
+        stream.synchronize()
+        back = np.empty(D, np.int32)
+        back[h_order] = dd_o.cpu().numpy()
+        wall_pm = time.perf_counter() - t0
+        assert np.array_equal(back, want), "the per-map route differs from the host evaluator"
+        t0 = time.perf_counter()
+        dd_t = torch.from_numpy(tup.view(np.uint8)).to(dev)
+        dd_l = torch.from_numpy(lxc.view(np.int16)).to(dev)
+        arr.verdicts_dev(dd_l, dd_t, D, dd_o, stream=stream.cuda_stream, mode=mode)
+        stream.synchronize()
+        back = dd_o.cpu().numpy()
+        wall_arr = time.perf_counter() - t0
+        r["from_host_data"] = {"tuples": D, "per_map_wall_s": wall_pm, "array_wall_s": wall_arr}
+        del d_t, d_l, dd_t, dd_l, dd_o
+    ceiling = bench_l4(torch, dev, stream, cl, argparse.Namespace(**{**vars(args), "cpu_seconds": 0}), threads)
+    u = res["uniform"]
+    return line("L4 verdicts/s across 256 endpoints (l4_array_kernel: the policy program array, endpoint ids "
+                "uniform per tuple)", n, u["kernel_ms"] * 1e-3, 18, "l4_array_kernel", cpu,
+                "cg_diag_l4_array_eval_host over the first copy, one thread", 1,
+                {"config": {"workload": "256 policy maps of config 2's 16,384-entry mix, config 2's tuples",
+                            "maps": E, "distinct_tuples": D, "tuples": n},
+                 "mixes": res, "single_map_ceiling_Gtuples_s": ceiling["value"] / 1e9})
 
 
 def bench_lpm(torch, dev, stream, cl, args, threads):
@@ -1033,6 +1181,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--cpu-seconds", type=float, default=5.0)
     ap.add_argument("--prewarm-seconds", type=float, default=0.3)
+    ap.add_argument("--array-tuples", type=int, default=1 << 26, help="l4_array: distinct tuples before tiling")
     args = ap.parse_args()
     global PREWARM_S
     PREWARM_S = args.prewarm_seconds
@@ -1046,7 +1195,7 @@ def main():
            "proxylib": bench_proxylib, "l4ipc": bench_l4ipc, "kafkawire": bench_kafka_wire, "httphost": bench_http_host, "httpraw": bench_http_raw,
            "httpfields": bench_http_fields, "memcache": bench_memcache, "cassandra": bench_cassandra,
            "kafkawirez": lambda *a: bench_kafka_wire(*a, codec_frac=0.5), "selcache": bench_selcache,
-           "selcache_cidr": bench_selcache_cidr}
+           "selcache_cidr": bench_selcache_cidr, "l4_array": bench_l4_array}
     for p in args.paths.split(","):
         print(json.dumps(fns[p](torch, dev, stream, cl, args, threads)), flush=True)
     cl.close()
