@@ -42,6 +42,10 @@ CG_DROP_POLICY = -133
 CG_DROP_FRAG_NOSUPPORT = -157
 CG_DROP_MISSED_TAIL_CALL = -140
 CG_POLICY_ARRAY_SLOTS = 65536
+CG_DROP_INVALID, CG_DROP_CT_INVALID_HDR, CG_DROP_CT_UNKNOWN_PROTO, CG_DROP_UNKNOWN_L3 = -134, -135, -137, -139
+CG_DROP_INVALID_EXTHDR = -156
+CG_FRAME_NOT_LOCAL, CG_FRAME_TO_HOST = -1, -2
+CG_ENDPOINT_F_HOST = 1
 
 CG_PF_DYN4, CG_PF_DYN6, CG_PF_FIX4, CG_PF_FIX6 = 1, 2, 4, 8
 CG_XDP_DROP, CG_XDP_PASS = 1, 2
@@ -231,6 +235,15 @@ SIGNATURES = {
     "cg_l4_array_verdicts_ipcache_dev": (C.c_int, [_u64, _u32, _u32, _u32, C.c_int, _p, _p, _p, _sz, _p, _p]),
     "cg_l4_array_verdicts_ipcache_host": (C.c_int, [_u64, _u32, _u32, _u32, C.c_int, _p, _p, _p, _sz, _p]),
     "cg_diag_l4_array_eval_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p]),
+    "cg_endpoint_map_create": (C.c_int, [_u64, _u32, C.POINTER(_u32)]),
+    "cg_endpoint_map_destroy": (C.c_int, [_u64, _u32]),
+    "cg_endpoint_map_update": (C.c_int, [_u64, _u32, _p, _p, _sz]),
+    "cg_endpoint_map_delete": (C.c_int, [_u64, _u32, _p, _sz]),
+    "cg_endpoint_map_lookup": (C.c_int, [_u64, _u32, _p, _p]),
+    "cg_endpoint_map_dump": (C.c_int, [_u64, _u32, _p, _p, _sz, C.POINTER(_sz)]),
+    "cg_l4_frames_verdicts_dev": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _u32, _p, _u32, _p, _p, _p, _p]),
+    "cg_l4_frames_verdicts_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _u32, _p, _u32, _p, _p, _p]),
+    "cg_diag_l4_frames_eval_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _u32, _p, _u32, _p, _p, _p, _p]),
 }
 
 

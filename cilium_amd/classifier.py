@@ -6,6 +6,9 @@ Mirrors the reference's entry points for the classification path:
   DumpToSlice/Flush) + batched ``policy_can_access`` (bpf/lib/policy.h:46-163)
 * ``PolicyArray`` — the policy program array ``cilium_policy[lxc_id]``
   (bpf/lib/maps.h:44-62): verdicts for a batch addressed to many endpoints
+* ``EndpointMap`` — pkg/maps/lxcmap (WriteEndpoint/DeleteEntry/DumpToMap), and
+  ``PolicyArray.frame_verdicts``: the ingress policy program from raw frames
+  (bpf/bpf_lxc.c:1030-1058)
 * ``PreFilter``  — pkg/datapath/prefilter (Insert/Delete/Dump with revisions)
   + batched XDP ``check_filters`` (bpf/bpf_xdp.c:88-184)
 * ``Classifier.update_http_policy`` / ``http_verdicts`` — Envoy
@@ -36,6 +39,11 @@ CIDR_DTYPE = np.dtype([("family", "u1"), ("prefixlen", "u1"), ("pad", "u1", (2,)
 KAFKA_REQ_DTYPE = np.dtype([("api_key", "<i2"), ("api_version", "<i2"), ("kind", "u1"), ("n_topics", "u1"),
                             ("policy", "<u2"), ("remote", "<u4"), ("client_id", "<u4"),
                             ("topic_ids", "<u4", (N.CG_KAFKA_MAX_TOPICS,))])
+ENDPOINT_KEY_DTYPE = np.dtype([("family", "u1"), ("pad", "u1", (3,)), ("addr", "u1", (16,))])
+ENDPOINT_INFO_DTYPE = np.dtype([("lxc_id", "<u2"), ("pad", "<u2"), ("flags", "<u4")])
+# cg_l4_frame_info: what the header walk found (cilium_gpu.h)
+FRAME_INFO_DTYPE = np.dtype([("t", L4_TUPLE_DTYPE), ("lxc_id", "<u2"), ("family", "u1"), ("pad", "u1")])
+assert ENDPOINT_KEY_DTYPE.itemsize == 20 and ENDPOINT_INFO_DTYPE.itemsize == 8 and FRAME_INFO_DTYPE.itemsize == 16
 assert L4_TUPLE_DTYPE.itemsize == 12 and KAFKA_REQ_DTYPE.itemsize == 64 and CIDR_DTYPE.itemsize == 20
 
 
@@ -93,6 +101,10 @@ class Classifier:
     def policy_array(self) -> "PolicyArray":
         """The policy program array: lxc_id → PolicyMap, verdicts across endpoints."""
         return PolicyArray(self)
+
+    def endpoint_map(self, max_entries: int = 0) -> "EndpointMap":
+        """cilium_lxc: a local endpoint's address → {lxc_id, flags}."""
+        return EndpointMap(self, max_entries)
 
     # ------------------------------------------------------------ LPM --
     def prefilter(self, dyn4: bool = False, dyn6: bool = False, fix4: bool = True, fix6: bool = True,
@@ -739,6 +751,138 @@ class PolicyArray:
         lxc, tuples, out = self._args(lxc_ids, tuples)
         N.check(N.lib.cg_diag_l4_array_eval_host(self.cl.h, self.id, mode, _p(lxc), _p(tuples), len(tuples), _p(out)))
         return out[:len(tuples)]
+
+    # ------------------------------------------------ from raw frames --
+    def _frame_args(self, raw, off, lxc_ids, endpoints, src_labels, ipcache, pkt_len, ignore_drop):
+        raw = np.ascontiguousarray(raw, np.uint8).reshape(-1)
+        off = np.ascontiguousarray(off, np.uint64).reshape(-1)
+        if len(off) < 1:
+            raise ValueError("off holds n + 1 offsets")
+        n = len(off) - 1
+        if int(off[-1]) > len(raw):  # the window [off[0], off[n]) is all the device reads
+            raise ValueError("off[n] lies past the end of raw")
+        lxc = None if lxc_ids is None else self._lxc(lxc_ids)
+        lab = None if src_labels is None else np.ascontiguousarray(src_labels, np.uint32).reshape(-1)
+        plen = None if pkt_len is None else np.ascontiguousarray(pkt_len, np.uint32).reshape(-1)
+        for a in (lxc, lab, plen):
+            if a is not None and len(a) != n:
+                raise ValueError("one lxc_id / src_label / pkt_len per frame")
+        mode = N.CG_L4_INGRESS | (N.CG_L4_IGNORE_DROP if ignore_drop else 0)
+        # a length-0 array still has to read as "given" to the resolver check
+        keep = [np.zeros(1, a.dtype) if a is not None and not len(a) else a for a in (lxc, lab, plen)]
+        return (raw, off, n, keep[0], endpoints.id if endpoints is not None else 0, keep[1],
+                ipcache.id if ipcache is not None else 0, keep[2], mode)
+
+    def frame_verdicts(self, raw, off, *, lxc_ids=None, endpoints: Optional["EndpointMap"] = None, src_labels=None,
+                       ipcache: Optional["IPCache"] = None, pkt_len=None, ignore_drop: bool = False,
+                       info: bool = False):
+        """The ingress policy program's verdict per raw Ethernet frame, frame i
+        = raw[off[i]:off[i+1]], parsed and judged on the device in one launch
+        (cg_l4_frames_verdicts_host).  Exactly one of lxc_ids / endpoints (an
+        EndpointMap looked up by destination address) and one of src_labels /
+        ipcache (resolving the source address).  pkt_len: skb->len for the
+        byte counters (default: the frame's length).  info=True also returns
+        the FRAME_INFO_DTYPE records."""
+        raw, off, n, lxc, ep, lab, ipc, plen, mode = self._frame_args(raw, off, lxc_ids, endpoints, src_labels,
+                                                                      ipcache, pkt_len, ignore_drop)
+        out = np.zeros(max(n, 1), np.int32)
+        fi = np.zeros(max(n, 1), FRAME_INFO_DTYPE) if info else None
+        N.check(N.lib.cg_l4_frames_verdicts_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep, _p(lab),
+                                                 ipc, _p(plen), _p(out), _p(fi)))
+        return (out[:n], fi[:n]) if info else out[:n]
+
+    def frame_verdicts_dev(self, d_raw, d_off, n: int, d_out, *, d_lxc_ids=None,
+                           endpoints: Optional["EndpointMap"] = None, d_src_labels=None,
+                           ipcache: Optional["IPCache"] = None, d_pkt_len=None, ignore_drop: bool = False,
+                           d_info=None, stream=None) -> None:
+        """Device buffers (u8 blob, n + 1 u64 offsets, i32 verdicts, optional
+        16-byte info records), async on `stream`."""
+        mode = N.CG_L4_INGRESS | (N.CG_L4_IGNORE_DROP if ignore_drop else 0)
+        N.check(N.lib.cg_l4_frames_verdicts_dev(self.cl.h, self.id, mode, _p(d_raw), _p(d_off), n, _p(d_lxc_ids),
+                                                endpoints.id if endpoints is not None else 0, _p(d_src_labels),
+                                                ipcache.id if ipcache is not None else 0, _p(d_pkt_len), _p(d_out),
+                                                _p(d_info), stream))
+
+    def frame_eval_host_diag(self, raw, off, *, lxc_ids=None, endpoints: Optional["EndpointMap"] = None,
+                             src_labels=None, ipcache: Optional["IPCache"] = None, pkt_len=None,
+                             ignore_drop: bool = False, info: bool = False, l4_off: bool = False):
+        """Diagnostics only: frame_verdicts by the kernel's own walk on the CPU
+        (no device, no counters).  l4_off=True appends the L4 offsets found."""
+        raw, off, n, lxc, ep, lab, ipc, plen, mode = self._frame_args(raw, off, lxc_ids, endpoints, src_labels,
+                                                                      ipcache, pkt_len, ignore_drop)
+        out = np.zeros(max(n, 1), np.int32)
+        fi = np.zeros(max(n, 1), FRAME_INFO_DTYPE) if info else None
+        lo = np.zeros(max(n, 1), np.uint32) if l4_off else None
+        N.check(N.lib.cg_diag_l4_frames_eval_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep, _p(lab),
+                                                  ipc, _p(plen), _p(out), _p(fi), _p(lo)))
+        res = (out[:n],) + ((fi[:n],) if info else ()) + ((lo[:n],) if l4_off else ())
+        return res if len(res) > 1 else res[0]
+
+
+class EndpointMap:
+    """pkg/maps/lxcmap (cilium_lxc) on the device: a local endpoint's IPv4 or
+    IPv6 address → {lxc_id, flags}, the map lookup_ip{4,6}_endpoint reads
+    (bpf/lib/eps.h:26-46) in front of the tail call into the policy array."""
+
+    def __init__(self, cl: Classifier, max_entries: int = 0):
+        self.cl = cl
+        v = C.c_uint32()
+        N.check(N.lib.cg_endpoint_map_create(cl.h, max_entries, C.byref(v)))
+        self.id = v.value
+
+    @staticmethod
+    def _keys(addrs) -> np.ndarray:
+        if isinstance(addrs, np.ndarray) and addrs.dtype == ENDPOINT_KEY_DTYPE:
+            return np.ascontiguousarray(addrs)
+        k = np.zeros(len(addrs), ENDPOINT_KEY_DTYPE)
+        for i, a in enumerate(addrs):
+            ip = ipaddress.ip_address(a)
+            k["family"][i] = ip.version
+            k["addr"][i, :len(ip.packed)] = np.frombuffer(ip.packed, np.uint8)
+        return k
+
+    def write_endpoints(self, addrs, lxc_ids, flags=0) -> None:
+        """WriteEndpoint for each address; all or nothing (cg_endpoint_map_update)."""
+        k = self._keys(addrs)
+        v = np.zeros(len(k), ENDPOINT_INFO_DTYPE)
+        v["lxc_id"], v["flags"] = lxc_ids, flags
+        N.check(N.lib.cg_endpoint_map_update(self.cl.h, self.id, _p(k) if len(k) else None,
+                                             _p(v) if len(k) else None, len(k)))
+
+    def write_endpoint(self, addr, lxc_id: int, host: bool = False) -> None:
+        """lxcmap.WriteEndpoint (lxcmap.go:160-180): an existing key is overwritten."""
+        self.write_endpoints([addr], [lxc_id], N.CG_ENDPOINT_F_HOST if host else 0)
+
+    def delete_entry(self, addr) -> None:
+        """lxcmap.DeleteEntry; CG_NOT_FOUND when the address is absent."""
+        k = self._keys(addr if isinstance(addr, (list, tuple, np.ndarray)) else [addr])
+        N.check(N.lib.cg_endpoint_map_delete(self.cl.h, self.id, _p(k) if len(k) else None, len(k)))
+
+    def lookup(self, addr) -> Optional[tuple[int, int]]:
+        """(lxc_id, flags), or None when the address is absent."""
+        k = self._keys([addr])
+        v = np.zeros(1, ENDPOINT_INFO_DTYPE)
+        rc = N.lib.cg_endpoint_map_lookup(self.cl.h, self.id, _p(k), _p(v))
+        if rc == N.CG_NOT_FOUND:
+            return None
+        N.check(rc)
+        return int(v["lxc_id"][0]), int(v["flags"][0])
+
+    def dump_to_map(self) -> dict:
+        """lxcmap.DumpToMap: {address string: (lxc_id, flags)}, IPv4 first, by address."""
+        n = C.c_size_t()
+        N.check(N.lib.cg_endpoint_map_dump(self.cl.h, self.id, None, None, 0, C.byref(n)))
+        k = np.zeros(max(n.value, 1), ENDPOINT_KEY_DTYPE)
+        v = np.zeros(max(n.value, 1), ENDPOINT_INFO_DTYPE)
+        N.check(N.lib.cg_endpoint_map_dump(self.cl.h, self.id, _p(k), _p(v), n.value, C.byref(n)))
+        out = {}
+        for c, x in zip(k[:n.value], v[:n.value]):
+            raw = bytes(c["addr"][:4]) if c["family"] == 4 else bytes(c["addr"])
+            out[str(ipaddress.ip_address(raw))] = (int(x["lxc_id"]), int(x["flags"]))
+        return out
+
+    def destroy(self) -> None:
+        N.check(N.lib.cg_endpoint_map_destroy(self.cl.h, self.id))
 
 
 def parse_cidr(s: str) -> np.ndarray:

@@ -13,7 +13,9 @@
 #include <string>
 #include <vector>
 
+#include "endpoint_map.h"
 #include "engine.h"
+#include "frame_walk.h"
 #include "http.h"
 #include "kafka.h"
 #include "kafka_wire.h"
@@ -79,6 +81,12 @@ PolicyMapState& get_map(Engine& e, uint32_t id) {
 PolicyArrayState& get_arr(Engine& e, uint32_t id) {
   auto it = e.arrays.find(id);
   if (it == e.arrays.end()) fail(CG_NOT_FOUND, "unknown policy array id");
+  return *it->second;
+}
+
+EndpointMapState& get_ep(Engine& e, uint32_t id) {
+  auto it = e.epmaps.find(id);
+  if (it == e.epmaps.end()) fail(CG_NOT_FOUND, "unknown endpoint map id");
   return *it->second;
 }
 
@@ -196,6 +204,7 @@ void cg_close(uint64_t h) {
     e->maps.clear();
     e->prefilters.clear();
     e->ipcaches.clear();
+    e->epmaps.clear();
     e->selcaches.clear();
     e->http.reset();
     e->kafka.reset();
@@ -607,8 +616,7 @@ struct L4ArrView {
   std::shared_ptr<L4ArrTables> keep;
   L4ArrDev dev;
 };
-static L4ArrView l4_array_view(Engine& e, uint32_t arr_id) {
-  std::lock_guard<std::mutex> lk(e.mu);
+static L4ArrView l4_array_view_locked(Engine& e, uint32_t arr_id) {  // the caller holds e.mu
   PolicyArrayState& a = get_arr(e, arr_id);
   std::vector<std::shared_ptr<DevTables>> members;
   std::vector<L4Dev> recs;
@@ -638,6 +646,10 @@ static L4ArrView l4_array_view(Engine& e, uint32_t arr_id) {
     a.slots_changed = false;
   }
   return {a.tab, a.dev};
+}
+static L4ArrView l4_array_view(Engine& e, uint32_t arr_id) {
+  std::lock_guard<std::mutex> lk(e.mu);
+  return l4_array_view_locked(e, arr_id);
 }
 
 static void l4_array_dev(Engine& e, uint32_t arr_id, const IpcView* iv, uint32_t mode, int family, const void* d_addr,
@@ -707,6 +719,207 @@ int cg_l4_array_verdicts_ipcache_host(uint64_t h, uint32_t arr_id, uint32_t ipc_
     e->require_gpu();
     const IpcView iv = ipc_view(*e, ipc_id);
     l4_array_host(*e, arr_id, &iv, mode, family, remote, lxc_ids, tuples, n, verdicts);
+  });
+}
+
+// ----------------------------------------------------- endpoint map ----
+// cilium_lxc with its values (endpoint_map.h), the control-plane calls of
+// pkg/maps/lxcmap.
+static EndpointMapState::Key make_ep_key(const cg_endpoint_key& k) {
+  if (k.family != 4 && k.family != 6) fail(CG_INVALID_ADDRESS, "endpoint key family must be 4 or 6");
+  EndpointMapState::Key out;
+  out.first = k.family;
+  out.second.fill(0);
+  memcpy(out.second.data(), k.addr, k.family == 4 ? 4 : 16);
+  return out;
+}
+
+int cg_endpoint_map_create(uint64_t h, uint32_t max_entries, uint32_t* ep_id) {
+  return guarded([&] {
+    auto e = get(h);
+    if (!ep_id) fail(CG_INVALID_ARGUMENT, "ep_id is NULL");
+    std::lock_guard<std::mutex> lk(e->mu);
+    auto p = std::make_unique<EndpointMapState>();
+    if (max_entries) p->max_entries = max_entries;
+    const uint32_t id = e->next_id++;
+    e->epmaps[id] = std::move(p);
+    *ep_id = id;
+  });
+}
+
+int cg_endpoint_map_destroy(uint64_t h, uint32_t ep_id) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    get_ep(*e, ep_id);
+    if (e->has_gpu()) dev_sync(*e, nullptr);
+    e->epmaps.erase(ep_id);
+  });
+}
+
+int cg_endpoint_map_update(uint64_t h, uint32_t ep_id, const cg_endpoint_key* keys, const cg_endpoint_info* values,
+                           size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    if (n && (!keys || !values)) fail(CG_INVALID_ARGUMENT, "NULL keys/values");
+    std::lock_guard<std::mutex> lk(e->mu);
+    EndpointMapState& p = get_ep(*e, ep_id);
+    // a key given twice in one batch keeps its last value, as sequential updates would
+    std::map<EndpointMapState::Key, cg_endpoint_info> batch;
+    for (size_t i = 0; i < n; ++i) batch[make_ep_key(keys[i])] = cg_endpoint_info{values[i].lxc_id, 0, values[i].flags};
+    size_t fresh = 0;
+    for (const auto& kv : batch) fresh += !p.entries.count(kv.first);
+    if (p.entries.size() + fresh > p.max_entries) fail(CG_MAP_FULL, "endpoint map full (max_entries)");
+    for (const auto& kv : batch) p.entries[kv.first] = kv.second;
+    p.dirty = true;
+  });
+}
+
+int cg_endpoint_map_delete(uint64_t h, uint32_t ep_id, const cg_endpoint_key* keys, size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    if (n && !keys) fail(CG_INVALID_ARGUMENT, "NULL keys");
+    std::lock_guard<std::mutex> lk(e->mu);
+    EndpointMapState& p = get_ep(*e, ep_id);
+    std::vector<EndpointMapState::Key> ks;
+    for (size_t i = 0; i < n; ++i) {
+      ks.push_back(make_ep_key(keys[i]));
+      if (!p.entries.count(ks.back())) fail(CG_NOT_FOUND, "endpoint map: no entry for key");
+    }
+    for (const auto& k : ks) p.entries.erase(k);
+    p.dirty = true;
+  });
+}
+
+int cg_endpoint_map_lookup(uint64_t h, uint32_t ep_id, const cg_endpoint_key* key, cg_endpoint_info* value) {
+  return guarded([&] {
+    auto e = get(h);
+    if (!key || !value) fail(CG_INVALID_ARGUMENT, "NULL key/value");
+    std::lock_guard<std::mutex> lk(e->mu);
+    EndpointMapState& p = get_ep(*e, ep_id);
+    auto it = p.entries.find(make_ep_key(*key));
+    if (it == p.entries.end()) fail(CG_NOT_FOUND, "endpoint map: no entry for key");
+    *value = it->second;
+  });
+}
+
+int cg_endpoint_map_dump(uint64_t h, uint32_t ep_id, cg_endpoint_key* keys, cg_endpoint_info* values, size_t cap,
+                         size_t* n) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    EndpointMapState& p = get_ep(*e, ep_id);
+    size_t i = 0;
+    for (const auto& [k, v] : p.entries) {
+      if (i >= cap) break;
+      if (keys) {
+        memset(&keys[i], 0, sizeof(cg_endpoint_key));
+        keys[i].family = k.first;
+        memcpy(keys[i].addr, k.second.data(), 16);
+      }
+      if (values) values[i] = v;
+      ++i;
+    }
+    if (n) *n = p.entries.size();
+  });
+}
+
+// ------------------------------------------- L4 verdicts from frames ----
+// One snapshot of the policy array, the endpoint map and the ipcache, taken
+// under one hold of the handle lock; the launch holds all three.
+struct FramesView {
+  L4ArrView arr;
+  std::shared_ptr<DevTables> ep_keep, ipc_keep;
+  EpMapDev ep{};
+  IpcacheDev ipc{};
+};
+static void check_frames_args(uint32_t mode, const void* lxc, uint32_t ep_id, const void* labels, uint32_t ipc_id) {
+  if ((mode & ~CG_L4_IGNORE_DROP) != CG_L4_INGRESS)
+    fail(CG_INVALID_ARGUMENT, "frame verdicts run the ingress program: mode is CG_L4_INGRESS [| CG_L4_IGNORE_DROP]");
+  if ((lxc != nullptr) == (ep_id != 0)) fail(CG_INVALID_ARGUMENT, "give lxc_ids or an endpoint map, not both or neither");
+  if ((labels != nullptr) == (ipc_id != 0))
+    fail(CG_INVALID_ARGUMENT, "give src_labels or an ipcache, not both or neither");
+}
+static FramesView frames_view(Engine& e, uint32_t arr_id, uint32_t ep_id, uint32_t ipc_id) {
+  std::lock_guard<std::mutex> lk(e.mu);
+  FramesView v;
+  v.arr = l4_array_view_locked(e, arr_id);
+  if (ep_id) {
+    EndpointMapState& p = get_ep(e, ep_id);
+    if (p.dirty) p.rebuild(e);
+    v.ep_keep = p.tab;
+    v.ep = p.dev;
+  }
+  if (ipc_id) {
+    IpcacheState& p = get_ipc(e, ipc_id);
+    if (p.dirty) p.rebuild(e);
+    v.ipc_keep = p.tab;
+    v.ipc = p.dev;
+  }
+  return v;
+}
+static void frames_launch(Engine& e, const FramesView& v, uint32_t mode, const uint8_t* d_raw, const uint64_t* d_off,
+                          size_t n, const uint16_t* d_lxc, const uint32_t* d_labels, const uint32_t* d_len,
+                          int32_t* d_out, void* d_info, void* st) {
+  check_launch(launch_l4_frames(v.arr.dev, v.ep_keep ? &v.ep : nullptr, v.ipc_keep ? &v.ipc : nullptr, d_raw, d_off, n,
+                                d_lxc, d_labels, d_len, d_out, d_info, mode, st, e.cus),
+               "l4 frames kernel launch");
+  v.arr.keep->own.fence.record(st);
+  fence(v.ep_keep, st);
+  fence(v.ipc_keep, st);
+}
+
+int cg_l4_frames_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
+                              const uint64_t* d_raw_off, size_t n, const uint16_t* d_lxc_ids, uint32_t ep_id,
+                              const uint32_t* d_src_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
+                              int32_t* d_verdicts, cg_l4_frame_info* d_info, void* stream) {
+  return guarded([&] {
+    auto e = get(h);
+    check_frames_args(mode, d_lxc_ids, ep_id, d_src_labels, ipc_id);
+    e->require_gpu();
+    if (!d_raw_off || (n && !d_verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
+    const FramesView v = frames_view(*e, arr_id, ep_id, ipc_id);
+    e->set_device();
+    frames_launch(*e, v, mode, d_raw, d_raw_off, n, d_lxc_ids, d_src_labels, d_pkt_len, d_verdicts, d_info,
+                  stream_of(*e, stream));
+  });
+}
+
+static void* stage_in(StagingSlot& sl, int i, const void* src, size_t bytes);
+
+int cg_l4_frames_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                               const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
+                               const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                               int32_t* verdicts, cg_l4_frame_info* info) {
+  return guarded([&] {
+    auto e = get(h);
+    check_frames_args(mode, lxc_ids, ep_id, src_labels, ipc_id);
+    e->require_gpu();
+    if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
+    const uint64_t lo = raw_off[0], bytes = raw_off[n] > lo ? raw_off[n] - lo : 0;
+    if (bytes && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
+    const FramesView v = frames_view(*e, arr_id, ep_id, ipc_id);
+    if (!n) return;
+    e->set_device();
+    auto lease = e->staging.acquire(e->device);
+    const auto st = (hipStream_t)lease->stream;
+    // the blob's window [raw_off[0], raw_off[n]) is what travels; the kernel adds the offsets to d_raw
+    const uint8_t* d_win = (const uint8_t*)stage_in(*lease, 0, raw + lo, bytes);
+    const uint8_t* d_raw = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(d_win) - lo);
+    const uint64_t* d_off = (const uint64_t*)stage_in(*lease, 1, raw_off, (n + 1) * 8);
+    const uint16_t* d_lxc = lxc_ids ? (const uint16_t*)stage_in(*lease, 2, lxc_ids, n * 2) : nullptr;
+    const uint32_t* d_lab = src_labels ? (const uint32_t*)stage_in(*lease, 3, src_labels, n * 4) : nullptr;
+    const uint32_t* d_len = pkt_len ? (const uint32_t*)stage_in(*lease, 4, pkt_len, n * 4) : nullptr;
+    int32_t* d_out = (int32_t*)lease->dev_buf(5, n * 4);
+    void* d_info = info ? lease->dev_buf(6, n * sizeof(cg_l4_frame_info)) : nullptr;
+    frames_launch(*e, v, mode, d_raw, d_off, n, d_lxc, d_lab, d_len, d_out, d_info, st);
+    int32_t* h_out = (int32_t*)lease->host_buf(5, n * 4);
+    hip_check(hipMemcpyAsync(h_out, d_out, n * 4, hipMemcpyDeviceToHost, st), "D2H");
+    void* h_info = info ? lease->host_buf(6, n * sizeof(cg_l4_frame_info)) : nullptr;
+    if (info) hip_check(hipMemcpyAsync(h_info, d_info, n * sizeof(cg_l4_frame_info), hipMemcpyDeviceToHost, st), "D2H");
+    hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+    memcpy(verdicts, h_out, n * 4);
+    if (info) memcpy(info, h_info, n * sizeof(cg_l4_frame_info));
   });
 }
 
@@ -2490,6 +2703,79 @@ int cg_diag_l4_array_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const
       const int which = l4_resolve(T, [&](uint32_t b) { return T.fp[b]; }, w[0], w1,
                                    (w1 >> 24) & CG_L4_F_FRAGMENT, &val);
       out[i] = l4_wrap(l4_verdict(which, val, w1 >> 24), mode);
+    }
+  });
+}
+
+// Per frame as l4_frames_kernel does it: frame_walk.h over the host views of
+// the array, the endpoint map and the ipcache.  No device, no counters.
+// l4_off (may be NULL): the L4 offset the walk found, 0 where it did not get
+// that far.
+int cg_diag_l4_frames_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
+                                const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                int32_t* verdicts, cg_l4_frame_info* info, uint32_t* l4_off) {
+  return guarded([&] {
+    auto e = get(h);
+    check_frames_args(mode, lxc_ids, ep_id, src_labels, ipc_id);
+    if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
+    const uint64_t wlo = raw_off[0], whi = raw_off[n];
+    if (whi > wlo && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
+    std::lock_guard<std::mutex> lk(e->mu);
+    PolicyArrayState& a = get_arr(*e, arr_id);
+    // the array as the kernel sees it: slot words over the members' host views
+    std::map<uint32_t, uint32_t> word;
+    std::vector<L4Dev> recs;
+    for (const auto& ref : a.refs) {
+      PolicyMapState& m = get_map(*e, ref.first);
+      if (m.dirty) m.rebuild(*e);
+      word.emplace(ref.first, (uint32_t)recs.size() + 1);
+      recs.push_back(m.host_view());
+    }
+    std::vector<uint32_t> slot(CG_POLICY_ARRAY_SLOTS, 0u);
+    for (uint32_t s = 0; s < CG_POLICY_ARRAY_SLOTS; ++s)
+      if (a.slot_map[s]) slot[s] = word[a.slot_map[s]];
+    if (recs.empty()) recs.push_back(L4Dev{});
+    const L4ArrDev A{slot.data(), recs.data()};
+    EpMapDev E{};
+    IpcacheDev ipc{};
+    if (ep_id) {
+      EndpointMapState& p = get_ep(*e, ep_id);
+      if (p.dirty) p.rebuild(*e);
+      E = p.host_view();
+    }
+    if (ipc_id) {
+      IpcacheState& p = get_ipc(*e, ipc_id);
+      if (p.dirty) p.rebuild(*e);
+      ipc = p.host_view();
+    }
+    const uint8_t* lo = raw + wlo;
+    const uint8_t* hi = whi > wlo ? raw + whi : lo;
+    for (size_t i = 0; i < n; ++i) {
+      uint64_t start;
+      const uint32_t len = frame_range(raw_off[i], raw_off[i + 1], wlo, whi, &start);
+      const uint8_t* base = raw + start;
+      auto ld = [&](uint32_t o) {
+        uint32_t v = 0;
+        for (int k = 0; k < 4; ++k) {
+          const uint8_t* p = base + o + k;
+          if (p >= lo && p < hi) v |= (uint32_t)*p << (8 * k);
+        }
+        return v;
+      };
+      auto count = [](const L4Dev&, uint32_t) {};
+      const uint32_t plen = pkt_len ? pkt_len[i] : len;
+      const uint32_t lxc = lxc_ids ? lxc_ids[i] : 0u, label = src_labels ? src_labels[i] : 0u;
+      cg_l4_frame_info fi;
+      uint32_t lo4 = 0;
+      int32_t v;
+      if (ep_id && ipc_id) v = frame_verdict<true, true>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
+      else if (ep_id) v = frame_verdict<true, false>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
+      else if (ipc_id) v = frame_verdict<false, true>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
+      else v = frame_verdict<false, false>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
+      verdicts[i] = v;
+      if (info) info[i] = fi;
+      if (l4_off) l4_off[i] = lo4;
     }
   });
 }

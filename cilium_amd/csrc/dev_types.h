@@ -680,10 +680,12 @@ CG_HD inline uint32_t ipc_ex6_hash(uint64_t hi, uint64_t lo) {
   x *= 0xBF58476D1CE4E5B9ull;
   return (uint32_t)(x >> 32);
 }
-// The exact /32 entry of a (host order): 1 found (*e), 0 not there.
-CG_HD inline int ipc_ex4_find(const IpcacheDev& t, uint32_t a, uint32_t h, uint64_t* e) {
-  for (uint32_t p = 0; p <= t.ex4_probes; ++p) {
-    const uint32_t* s = t.ex4 + 4 * (size_t)((h + p) & t.ex4_mask);
+// The exact tables' search, over any table of that slot layout (the ipcache's
+// /32 and /128 entries, the endpoint map): 1 found (*e), 0 not there.  a in
+// host order; h the first slot to look at.
+CG_HD inline int ex4_find(const uint32_t* tab, uint32_t mask, uint32_t probes, uint32_t a, uint32_t h, uint64_t* e) {
+  for (uint32_t p = 0; p <= probes; ++p) {
+    const uint32_t* s = tab + 4 * (size_t)((h + p) & mask);
     if (!s[1]) return 0;
     if (s[0] == a) {
       *e = (uint64_t)s[3] << 32 | s[2];
@@ -692,9 +694,10 @@ CG_HD inline int ipc_ex4_find(const IpcacheDev& t, uint32_t a, uint32_t h, uint6
   }
   return 0;
 }
-CG_HD inline int ipc_ex6_find(const IpcacheDev& t, uint64_t hi, uint64_t lo, uint32_t h, uint64_t* e) {
-  for (uint32_t p = 0; p <= t.ex6_probes; ++p) {
-    const uint64_t* s = t.ex6 + 4 * (size_t)((h + p) & t.ex6_mask);
+CG_HD inline int ex6_find(const uint64_t* tab, uint32_t mask, uint32_t probes, uint64_t hi, uint64_t lo, uint32_t h,
+                          uint64_t* e) {
+  for (uint32_t p = 0; p <= probes; ++p) {
+    const uint64_t* s = tab + 4 * (size_t)((h + p) & mask);
     if (!s[3]) return 0;
     if (s[0] == hi && s[1] == lo) {
       *e = s[2];
@@ -702,6 +705,12 @@ CG_HD inline int ipc_ex6_find(const IpcacheDev& t, uint64_t hi, uint64_t lo, uin
     }
   }
   return 0;
+}
+CG_HD inline int ipc_ex4_find(const IpcacheDev& t, uint32_t a, uint32_t h, uint64_t* e) {
+  return ex4_find(t.ex4, t.ex4_mask, t.ex4_probes, a, h, e);
+}
+CG_HD inline int ipc_ex6_find(const IpcacheDev& t, uint64_t hi, uint64_t lo, uint32_t h, uint64_t* e) {
+  return ex6_find(t.ex6, t.ex6_mask, t.ex6_probes, hi, lo, h, e);
 }
 
 // ---- IPv4: 256-entry chunks in one of three encodings (ipcache.cc) ------
@@ -932,6 +941,17 @@ CG_HDI uint32_t ipc_v6_identity(const IpcacheDev& ipc, uint64_t hi, uint64_t lo,
     v = (uint32_t)ipc_v6_search_value(ipc, hi, lo, en.x, en.y, en.z);
   return v;
 }
+
+// ------------------------------------------------------- endpoint map ----
+// cilium_lxc (bpf/lib/maps.h, lookup_ip{4,6}_endpoint bpf/lib/eps.h:26-46): the
+// local endpoints by address, as exact tables of the ipcache's /32 and /128
+// slot layout and hashes (ex4_find / ex6_find).  An entry is lxc_id (bits
+// 0..15) | flags << 32.
+struct EpMapDev {
+  const uint32_t* ex4;
+  const uint64_t* ex6;
+  uint32_t ex4_mask, ex6_mask, ex4_probes, ex6_probes;
+};
 
 // ------------------------------------------------------- selector cache ----
 // Label selectors over the identity cache (selcache.h, kernels_selcache.hip;

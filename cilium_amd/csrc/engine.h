@@ -159,6 +159,7 @@ struct PolicyMapState;
 struct PolicyArrayState;
 struct PrefilterState;
 struct IpcacheState;
+struct EndpointMapState;
 struct SelcacheState;
 struct HttpSnapshot;
 struct KafkaSnapshot;
@@ -176,6 +177,7 @@ struct Engine {
   std::map<uint32_t, std::unique_ptr<PolicyArrayState>> arrays;  // policy program arrays (l4_array.h)
   std::map<uint32_t, std::unique_ptr<PrefilterState>> prefilters;
   std::map<uint32_t, std::unique_ptr<IpcacheState>> ipcaches;
+  std::map<uint32_t, std::unique_ptr<EndpointMapState>> epmaps;  // cilium_lxc (endpoint_map.h)
   std::map<uint32_t, std::unique_ptr<SelcacheState>> selcaches;
   std::shared_ptr<HttpSnapshot> http;
   std::shared_ptr<KafkaSnapshot> kafka;

@@ -66,42 +66,8 @@ void IpcacheState::build_tables() {
       else v6.emplace_back(key128(k), k.plen, resolved(v));
     }
   }
-  // open addressing at load <= 1/4 (a lookup's first slot is nearly always
-  // the answer or empty), linear probing; the longest probe sequence bounds
-  // every lookup
-  {
-    uint32_t cap = 16;
-    while (cap < 4 * x4.size()) cap <<= 1;
-    ex4.assign(4 * (size_t)cap, 0);
-    ex4_mask = cap - 1;
-    ex4_probes = 0;
-    for (const auto& [a, e] : x4) {
-      uint32_t p = 0;
-      while (ex4[4 * (size_t)((ipc_ex4_hash(a) + p) & ex4_mask) + 1]) ++p;
-      uint32_t* sl = &ex4[4 * (size_t)((ipc_ex4_hash(a) + p) & ex4_mask)];
-      sl[0] = a;
-      sl[1] = 1;
-      sl[2] = (uint32_t)e;
-      sl[3] = (uint32_t)(e >> 32);
-      ex4_probes = std::max(ex4_probes, p);
-    }
-    cap = 16;
-    while (cap < 4 * x6.size()) cap <<= 1;
-    ex6.assign(4 * (size_t)cap, 0);
-    ex6_mask = cap - 1;
-    ex6_probes = 0;
-    for (const auto& [k, e] : x6) {
-      const uint32_t h = ipc_ex6_hash(k.first, k.second);
-      uint32_t p = 0;
-      while (ex6[4 * (size_t)((h + p) & ex6_mask) + 3]) ++p;
-      uint64_t* sl = &ex6[4 * (size_t)((h + p) & ex6_mask)];
-      sl[0] = k.first;
-      sl[1] = k.second;
-      sl[2] = e;
-      sl[3] = 1;
-      ex6_probes = std::max(ex6_probes, p);
-    }
-  }
+  build_exact4(x4, &ex4, &ex4_mask, &ex4_probes);
+  build_exact6(x6, &ex6, &ex6_mask, &ex6_probes);
   std::sort(v4.begin(), v4.end());
   l16.assign(65536, kIpcMiss);
   chunks.clear();

@@ -3,6 +3,7 @@
 // device longest-prefix structures (dev_types.h IpcacheDev).
 #pragma once
 
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <vector>
@@ -12,6 +13,49 @@
 #include "lpm.h"
 
 namespace cg {
+
+// The exact tables of dev_types.h (ex4_find / ex6_find) from {address, entry}
+// pairs, for the ipcache's full-length prefixes and the endpoint map: open
+// addressing at load <= 1/4 (a lookup's first slot is nearly always the
+// answer or empty), linear probing; the longest probe sequence bounds every
+// lookup.  v4 addresses in host order, v6 as (high word, low word).
+inline void build_exact4(const std::vector<std::pair<uint32_t, uint64_t>>& x4, std::vector<uint32_t>* tab,
+                         uint32_t* mask, uint32_t* probes) {
+  uint32_t cap = 16;
+  while (cap < 4 * x4.size()) cap <<= 1;
+  tab->assign(4 * (size_t)cap, 0);
+  *mask = cap - 1;
+  *probes = 0;
+  for (const auto& [a, e] : x4) {
+    uint32_t p = 0;
+    while ((*tab)[4 * (size_t)((ipc_ex4_hash(a) + p) & *mask) + 1]) ++p;
+    uint32_t* sl = &(*tab)[4 * (size_t)((ipc_ex4_hash(a) + p) & *mask)];
+    sl[0] = a;
+    sl[1] = 1;
+    sl[2] = (uint32_t)e;
+    sl[3] = (uint32_t)(e >> 32);
+    *probes = std::max(*probes, p);
+  }
+}
+inline void build_exact6(const std::vector<std::pair<std::pair<uint64_t, uint64_t>, uint64_t>>& x6,
+                         std::vector<uint64_t>* tab, uint32_t* mask, uint32_t* probes) {
+  uint32_t cap = 16;
+  while (cap < 4 * x6.size()) cap <<= 1;
+  tab->assign(4 * (size_t)cap, 0);
+  *mask = cap - 1;
+  *probes = 0;
+  for (const auto& [k, e] : x6) {
+    const uint32_t h = ipc_ex6_hash(k.first, k.second);
+    uint32_t p = 0;
+    while ((*tab)[4 * (size_t)((h + p) & *mask) + 3]) ++p;
+    uint64_t* sl = &(*tab)[4 * (size_t)((h + p) & *mask)];
+    sl[0] = k.first;
+    sl[1] = k.second;
+    sl[2] = e;
+    sl[3] = 1;
+    *probes = std::max(*probes, p);
+  }
+}
 
 struct IpcacheState {
   uint32_t max_entries = 512000;  // ipcache.go:36 MaxEntries, node_config.h:61

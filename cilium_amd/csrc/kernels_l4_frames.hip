@@ -1,0 +1,130 @@
+// kernels_l4_frames.hip — L4 verdicts from raw frames: the endpoint's ingress
+// policy program from the Ethernet header on (frame_walk.h), per frame of a
+// blob, on the policy program array of kernels_l4_array.hip.
+//
+// One lane per frame, grid-stride.  A lane reads its two offsets (coalesced
+// across the wave), then the header fields it needs as aligned 4-byte words
+// with the bytes shifted out (frame starts have every alignment), the
+// endpoint map and the ipcache as its frame asks, and walks the slot's map as
+// l4_array_kernel does.  Counters go to the selected map's own array.
+#include <hip/hip_runtime.h>
+
+#include <map>
+#include <mutex>
+
+#include "../../include/cilium_gpu.h"
+#include "dev_types.h"
+#include "frame_walk.h"
+#include "kernels.h"
+
+namespace cg {
+
+namespace {
+
+constexpr int kFrmThreads = 256;
+
+// The four bytes at p, read as the two aligned words that hold them.  [lo, hi)
+// is the blob's window: words that lie inside it whole are loaded as words;
+// at the window's two edges the bytes are read one by one, and a byte outside
+// the window reads as 0 (the walk never uses one: it checks the frame's
+// length first, and a frame lies inside the window).
+__device__ __forceinline__ uint32_t frame_word(const uint8_t* p, const uint8_t* lo, const uint8_t* hi) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  const uint8_t* w = reinterpret_cast<const uint8_t*>(a & ~(uintptr_t)3);
+  const uint32_t sh = (uint32_t)(a & 3) * 8;
+  if (w >= lo && w + 8 <= hi) {
+    const uint32_t w0 = reinterpret_cast<const uint32_t*>(w)[0];
+    if (sh == 0) return w0;
+    const uint32_t w1 = reinterpret_cast<const uint32_t*>(w)[1];
+    return (w0 >> sh) | (w1 << (32 - sh));
+  }
+  uint32_t v = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (p + k >= lo && p + k < hi) v |= (uint32_t)p[k] << (8 * k);
+  return v;
+}
+
+template <bool kEp, bool kIpc>
+__global__ __launch_bounds__(kFrmThreads) void l4_frames_kernel(L4ArrDev A, EpMapDev E, IpcacheDev ipc,
+                                                                const uint8_t* __restrict__ raw,
+                                                                const uint64_t* __restrict__ off, size_t n,
+                                                                const uint16_t* __restrict__ lxc,
+                                                                const uint32_t* __restrict__ labels,
+                                                                const uint32_t* __restrict__ pkt_len,
+                                                                int32_t* __restrict__ out, uint4* __restrict__ info,
+                                                                uint32_t mode) {
+  const uint64_t wlo = off[0], whi = off[n];
+  const uint8_t* lo = raw + wlo;
+  const uint8_t* hi = whi > wlo ? raw + whi : lo;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    uint64_t start;
+    const uint32_t len = frame_range(off[i], off[i + 1], wlo, whi, &start);
+    const uint8_t* base = raw + start;
+    const uint32_t plen = pkt_len ? __builtin_nontemporal_load(pkt_len + i) : len;
+    const uint32_t id = kEp ? 0u : (uint32_t)__builtin_nontemporal_load(lxc + i);
+    const uint32_t label = kIpc ? 0u : __builtin_nontemporal_load(labels + i);
+    cg_l4_frame_info fi;
+    uint32_t l4_off;
+    const int32_t v = frame_verdict<kEp, kIpc>(
+        A, E, ipc, [&](uint32_t o) { return frame_word(base + o, lo, hi); }, len, id, label, plen, mode, &fi, &l4_off,
+        [&](const L4Dev& t, uint32_t entry) {
+          atomicAdd(&t.counters[2 * entry], 1ULL);
+          atomicAdd(&t.counters[2 * entry + 1], (unsigned long long)plen);
+        });
+    __builtin_nontemporal_store(v, out + i);
+    if (info) {
+      uint4 r;
+      r.x = fi.t.identity;
+      r.y = (uint32_t)fi.t.dport | (uint32_t)fi.t.proto << 16 | (uint32_t)fi.t.flags << 24;
+      r.z = fi.t.len;
+      r.w = (uint32_t)fi.lxc_id | (uint32_t)fi.family << 16;
+      info[i] = r;
+    }
+  }
+}
+
+int resident_blocks(const void* fn) {
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, int> cache;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache.find({fn, dev});
+  if (it == cache.end()) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kFrmThreads, 0) != hipSuccess || nb < 1) nb = 1;
+    it = cache.emplace(std::make_pair(fn, dev), nb).first;
+  }
+  return it->second;
+}
+
+template <bool kEp, bool kIpc>
+int launch_t(const L4ArrDev& A, const EpMapDev& E, const IpcacheDev& ipc, const uint8_t* raw, const uint64_t* off,
+             size_t n, const uint16_t* lxc, const uint32_t* labels, const uint32_t* pkt_len, int32_t* out, void* info,
+             uint32_t mode, void* stream, int cus) {
+  // sized as l4_array_kernel: grid-stride over exactly the blocks resident at once
+  size_t need = (n + kFrmThreads - 1) / kFrmThreads;
+  const size_t cap = (size_t)cus * resident_blocks((const void*)l4_frames_kernel<kEp, kIpc>);
+  if (need > cap) need = cap;
+  hipLaunchKernelGGL((l4_frames_kernel<kEp, kIpc>), dim3((unsigned)need), dim3(kFrmThreads), 0, (hipStream_t)stream, A,
+                     E, ipc, raw, off, n, lxc, labels, pkt_len, out, (uint4*)info, mode);
+  return (int)hipGetLastError();
+}
+
+}  // namespace
+
+int launch_l4_frames(const L4ArrDev& A, const EpMapDev* E, const IpcacheDev* ipc, const uint8_t* raw,
+                     const uint64_t* off, size_t n, const uint16_t* lxc, const uint32_t* labels,
+                     const uint32_t* pkt_len, int32_t* out, void* info, uint32_t mode, void* stream, int cus) {
+  if (n == 0) return 0;
+  const EpMapDev e = E ? *E : EpMapDev{};
+  const IpcacheDev c = ipc ? *ipc : IpcacheDev{};
+  if (E && ipc) return launch_t<true, true>(A, e, c, raw, off, n, lxc, labels, pkt_len, out, info, mode, stream, cus);
+  if (E) return launch_t<true, false>(A, e, c, raw, off, n, lxc, labels, pkt_len, out, info, mode, stream, cus);
+  if (ipc) return launch_t<false, true>(A, e, c, raw, off, n, lxc, labels, pkt_len, out, info, mode, stream, cus);
+  return launch_t<false, false>(A, e, c, raw, off, n, lxc, labels, pkt_len, out, info, mode, stream, cus);
+}
+
+}  // namespace cg

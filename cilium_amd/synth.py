@@ -717,3 +717,112 @@ def label_repository(n_rules: int = 10000, seed: int = SEED):
             subj = R.EndpointSelector.of({key(3): val(3)}, [(key(1), "In", (val(1), val(1)))])
         rules.append(R.Rule(subj, direction(R.IngressRule), direction(R.EgressRule) if rng.random() < 0.5 else []))
     return R.Repository(rules)
+
+
+# ------------------------------------------------- L4 from raw frames
+def l4_frames(n: int, dst4: np.ndarray, dst6: np.ndarray, src4: np.ndarray, src6: np.ndarray,
+              dports_be: np.ndarray, seed: int = SEED, min_len: int = 64, max_len: int = 160, snap: int = 0,
+              mix: tuple = (0.80, 0.15, 0.05), ext_share: float = 0.05, port_hit: float = 0.6):
+    """Ethernet frames for PolicyArray.frame_verdicts: (raw, off, pkt_len).
+
+    mix = shares of {IPv4 TCP/UDP, IPv6 TCP/UDP, the rest}.  IPv4: 4% carry
+    options (ihl 6..15), 1% are fragments (MF or an offset), some set DF.
+    IPv6: ext_share of them carry 1..4 extension headers (HOP, ROUTING, DEST,
+    AUTH; a few end in NONE or FRAGMENT).  The rest: ICMP and ICMPv6 of
+    several types, protocols 47 / 132, ARP and VLAN ethertypes, and frames
+    truncated anywhere from 0 bytes to the middle of the L4 header.
+    Addresses come from the pools (dst*/src*: (k, 4) and (k, 16) u8, network
+    order); destination ports from dports_be (u16 as stored) with probability
+    port_hit, else uniform.  A frame's wire length is uniform in [min_len,
+    max_len] (raised to hold its headers); snap > 0 cuts the captured bytes to
+    snap, pkt_len keeps the wire length."""
+    rng = np.random.default_rng(seed ^ 0xF4A3)
+    dst4, src4 = (np.ascontiguousarray(a, np.uint8).reshape(-1, 4) for a in (dst4, src4))
+    dst6, src6 = (np.ascontiguousarray(a, np.uint8).reshape(-1, 16) for a in (dst6, src6))
+    dports_be = np.ascontiguousarray(dports_be, np.uint16)
+    wire = rng.integers(min_len, max_len + 1, n).astype(np.int64)
+    r = rng.random(n)
+    v4 = r < mix[0]
+    v6 = ~v4 & (r < mix[0] + mix[1])
+    rest = ~v4 & ~v6
+    sub = rng.integers(0, 8, n)  # the rest: 0-1 ICMP, 2-3 ICMPv6, 4 other protocol, 5 non-IP, 6-7 truncated v4 / v6
+    fam4 = v4 | (rest & np.isin(sub, (0, 1, 4, 6)))
+    fam6 = v6 | (rest & np.isin(sub, (2, 3, 7)))
+    nonip = rest & (sub == 5)
+    proto = np.where(rng.random(n) < 0.5, 6, 17).astype(np.int64)
+    proto[rest & (sub <= 1)] = 1
+    proto[rest & np.isin(sub, (2, 3))] = 58
+    other = rest & (sub == 4)
+    proto[other] = rng.choice([47, 132, 2, 50], int(other.sum()))
+    # IPv4 header length, IPv6 extension chains (built per frame: they are few)
+    ihl = np.where(rng.random(n) < 0.04, rng.integers(6, 16, n), 5).astype(np.int64)
+    l4_off = np.where(fam4, 14 + 4 * ihl, 54).astype(np.int64)
+    chains = {}
+    for i in np.flatnonzero(fam6 & (rng.random(n) < ext_share)):
+        k = int(rng.choice([1, 1, 2, 2, 3, 3, 4]))
+        kinds = [int(x) for x in rng.choice([0, 43, 60, 51], k)]
+        last = int(proto[i]) if rng.random() < 0.9 else int(rng.choice([59, 44]))
+        chain = bytearray()
+        for j, _ in enumerate(kinds):
+            nxt = kinds[j + 1] if j + 1 < k else last
+            hl = int(rng.integers(0, 3))
+            size = (hl + 2) * 4 if nxt == 51 else (hl + 1) * 8  # the size the walk will step over
+            chain += bytes([nxt, hl]) + bytes(rng.integers(0, 256, size - 2, dtype=np.uint8))
+        chains[int(i)] = (kinds[0], bytes(chain))
+        l4_off[i] = 54 + len(chain)
+    wire = np.maximum(wire, l4_off + 20)
+    cap = np.minimum(wire, snap) if snap else wire.copy()
+    trunc = rest & (sub >= 6)
+    cap[trunc] = np.minimum(cap[trunc], rng.integers(0, l4_off[trunc] + 15))
+    W = int(cap.max()) if n else 0
+    Wb = max(W, int(l4_off.max()) + 20 if n else 0)
+    buf = rng.integers(0, 256, (n, Wb), dtype=np.uint8)
+    rows = np.arange(n)
+
+    def put(cols, vals, sel=None):
+        rr = rows if sel is None else rows[sel]
+        buf[rr, cols if np.isscalar(cols) else (cols if sel is None else cols[sel])] = \
+            vals if np.isscalar(vals) or sel is None else vals[sel]
+
+    et = np.where(fam4, 0x0800, np.where(fam6, 0x86DD, np.where(rng.random(n) < 0.5, 0x0806, 0x8100)))
+    put(12, et >> 8)
+    put(13, et & 0xFF)
+    # IPv4
+    put(14, 0x40 | ihl, fam4)
+    frag = np.zeros(n, np.int64)
+    fr = rng.random(n)
+    frag[fr < 0.3] = 0x4000  # DF: not a fragment
+    frag[fr < 0.01] = 0x2000  # MF
+    frag[fr < 0.005] = rng.integers(1, 0x2000, int((fr < 0.005).sum()))  # an offset
+    put(20, frag >> 8, fam4)
+    put(21, frag & 0xFF, fam4)
+    put(23, proto, fam4)
+    d4 = dst4[rng.integers(0, len(dst4), n)]
+    s4 = src4[rng.integers(0, len(src4), n)]
+    i4 = np.flatnonzero(fam4)
+    buf[i4, 26:30] = s4[i4]
+    buf[i4, 30:34] = d4[i4]
+    # IPv6
+    i6 = np.flatnonzero(fam6)
+    put(14, 0x60, fam6)
+    put(20, proto, fam6)
+    buf[i6, 22:38] = src6[rng.integers(0, len(src6), len(i6))]
+    buf[i6, 38:54] = dst6[rng.integers(0, len(dst6), len(i6))]
+    for i, (first, chain) in chains.items():
+        buf[i, 20] = first
+        buf[i, 54:54 + len(chain)] = np.frombuffer(chain, np.uint8)
+    # L4: destination port (as stored) at l4_off + 2, ICMP type at l4_off
+    uni = rng.integers(0, 65536, n).astype(np.uint16)
+    dp = np.where(rng.random(n) < port_hit, dports_be[rng.integers(0, len(dports_be), n)], uni) if len(dports_be) \
+        else uni
+    ip = fam4 | fam6
+    put(l4_off + 2, dp & 0xFF, ip)
+    put(l4_off + 3, dp >> 8, ip)
+    icmp = ip & ((proto == 1) | (proto == 58))
+    types = np.where(proto == 1, rng.choice([0, 3, 8, 8, 11, 5], n), rng.choice([1, 128, 128, 129, 135, 3], n))
+    put(l4_off, types, icmp)
+    keep = np.arange(Wb)[None, :] < cap[:, None]
+    raw = buf[keep]
+    off = np.zeros(n + 1, np.uint64)
+    np.cumsum(cap, out=off[1:])
+    return raw, off, wire.astype(np.uint32)

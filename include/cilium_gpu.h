@@ -221,6 +221,119 @@ int cg_l4_array_verdicts_ipcache_host(uint64_t h, uint32_t arr_id, uint32_t ipc_
                                       const void* remote, const uint16_t* lxc_ids, const cg_l4_tuple* tuples,
                                       size_t n, int32_t* verdicts);
 
+/* The endpoint map, cilium_lxc (bpf/lib/maps.h, struct endpoint_key /
+ * endpoint_info bpf/lib/common.h:147-173, lookup_ip{4,6}_endpoint
+ * bpf/lib/eps.h:26-46, pkg/maps/lxcmap/lxcmap.go): a local endpoint's address
+ * -> {lxc_id, flags}.  On the device it is an exact-match table, published by
+ * swap like every other table.  cg_prefilter_set_endpoints keeps its own
+ * membership set. */
+typedef struct {
+  uint8_t family;   /* 4 or 6 */
+  uint8_t pad[3];
+  uint8_t addr[16]; /* network byte order; v4 uses addr[0..3] */
+} cg_endpoint_key;
+typedef struct {
+  uint16_t lxc_id;
+  uint16_t pad;
+  uint32_t flags;   /* CG_ENDPOINT_F_* */
+} cg_endpoint_info;
+#define CG_ENDPOINT_F_HOST 1u /* EndpointFlagHost, lxcmap.go:91-92 */
+/* max_entries 0 = MaxEntries 65535 (lxcmap.go:33). */
+int cg_endpoint_map_create(uint64_t h, uint32_t max_entries, uint32_t* ep_id);
+int cg_endpoint_map_destroy(uint64_t h, uint32_t ep_id);
+/* WriteEndpoint (lxcmap.go:160-180) for each pair; an existing key is
+ * overwritten.  All-or-nothing as cg_ipcache_update: CG_INVALID_ADDRESS for a
+ * family other than 4 / 6, CG_MAP_FULL when the batch would exceed
+ * max_entries, and nothing is applied. */
+int cg_endpoint_map_update(uint64_t h, uint32_t ep_id, const cg_endpoint_key* keys, const cg_endpoint_info* values,
+                           size_t n);
+/* DeleteEntry (lxcmap.go:195-205); CG_NOT_FOUND (nothing deleted) if any key is absent. */
+int cg_endpoint_map_delete(uint64_t h, uint32_t ep_id, const cg_endpoint_key* keys, size_t n);
+int cg_endpoint_map_lookup(uint64_t h, uint32_t ep_id, const cg_endpoint_key* key, cg_endpoint_info* value);
+/* DumpToMap (lxcmap.go:207-216): keys in (family, address) order; *n gets the total. */
+int cg_endpoint_map_dump(uint64_t h, uint32_t ep_id, cg_endpoint_key* keys, cg_endpoint_info* values, size_t cap,
+                         size_t* n);
+
+/* L4 verdicts from raw frames: the endpoint's ingress policy program,
+ * handle_policy (bpf/bpf_lxc.c:1030-1058), from the Ethernet header on.  Frame
+ * i is raw[raw_off[i] .. raw_off[i+1]) (n + 1 offsets, as the raw HTTP path);
+ * one launch does the header walk of ipv4_policy / ipv6_policy
+ * (bpf_lxc.c:890-950, :744-816: ipv6_hdrlen lib/ipv6.h:61-98, the tuple
+ * extraction of ct_lookup4/6 lib/conntrack.h:467-556, :310-400 and the CT_NEW
+ * reversal :579-584) and then policy_can_access_ingress(src_label, dport,
+ * nexthdr, is_fragment) on the map in the endpoint's slot of the policy
+ * array, with the entry's packets and bytes advancing as in
+ * cg_l4_array_verdicts_*.  The program is the one built with CONNTRACK over an
+ * empty conntrack table: every packet is CT_NEW, tc_index and cb[CB_POLICY]
+ * are 0.  skb_load_bytes(off, n) and revalidate_data fail when off + n passes
+ * the frame's length.
+ *
+ * mode: CG_L4_INGRESS [| CG_L4_IGNORE_DROP]; anything else is
+ * CG_INVALID_ARGUMENT.  Exactly one of each resolver pair is given (both or
+ * neither: CG_INVALID_ARGUMENT):
+ *  - the endpoint: lxc_ids[i] (the tail call's index), or ep_id != 0: the
+ *    endpoint map looked up by the packet's destination address, the lookup
+ *    in front of the tail call in from-netdev / from-overlay
+ *    (bpf_netdev.c:414-420, :241-247);
+ *  - cb[CB_SRC_LABEL]: src_labels[i], or ipc_id != 0: the ipcache resolution
+ *    of the packet's source address exactly as cg_l4_array_verdicts_ipcache_*
+ *    resolve a remote address (miss or sec_label 0: CG_WORLD_ID).  The
+ *    HOST_ID exception and the packet-mark identity of bpf_netdev.c:370-389
+ *    belong to the from-host caller and are not modelled.
+ * pkt_len[i] is skb->len for the byte counters; NULL: the frame's length.
+ *
+ * Order with lxc_ids (tail_call + handle_policy):
+ *  1. empty slot: CG_DROP_MISSED_TAIL_CALL; nothing is read, no counter moves;
+ *  2. frame shorter than 14 bytes: CG_DROP_INVALID (the reference never sees
+ *     such an skb; the engine treats the missing ethertype as an invalid
+ *     packet);
+ *  3. ethertype other than 0x0800 / 0x86DD: CG_DROP_UNKNOWN_L3;
+ *  4. the walk: its DROP_* codes are returned as they are (neither the ingress
+ *     wrapper nor CG_L4_IGNORE_DROP touches them);
+ *  5. the source identity;  6. the policy verdict under `mode`.
+ * Order with ep_id:
+ *  1. frame shorter than 14 bytes or a non-IP ethertype: CG_FRAME_NOT_LOCAL;
+ *  2. IP header short (14 + 20 / 14 + 40 bytes): CG_DROP_INVALID;
+ *  3. destination address not in the map: CG_FRAME_NOT_LOCAL;
+ *  4. an entry with CG_ENDPOINT_F_HOST: CG_FRAME_TO_HOST;
+ *  5. else as above from step 1 with the found lxc_id.
+ * CG_FRAME_NOT_LOCAL and CG_FRAME_TO_HOST are the engine's own: they lie
+ * outside the DROP_* range and mean "no policy program ran" (from-netdev
+ * forwards such packets elsewhere).
+ *
+ * A frame whose range runs backwards is empty.  The device reads only bytes
+ * in [raw + raw_off[0], raw + raw_off[n]); a frame range that leaves that
+ * window is cut to it.  The call takes one snapshot of the array, the
+ * endpoint map and the ipcache under the handle lock, and the launch holds
+ * all three. */
+#define CG_DROP_INVALID (-134)          /* bpf/lib/common.h */
+#define CG_DROP_CT_INVALID_HDR (-135)
+#define CG_DROP_CT_UNKNOWN_PROTO (-137)
+#define CG_DROP_UNKNOWN_L3 (-139)
+#define CG_DROP_INVALID_EXTHDR (-156)
+#define CG_FRAME_NOT_LOCAL (-1)
+#define CG_FRAME_TO_HOST (-2)
+/* What the walk found, 16 bytes per frame; fields of a stage the frame did
+ * not reach are 0.  t.len (the length counted) and family are set once the
+ * frame is read, lxc_id once it is known, t.proto with tuple.nexthdr,
+ * t.dport (after the reversal; ICMP echo request: the raw u16 8 / 128) and
+ * t.flags (CG_L4_F_INGRESS [| CG_L4_F_FRAGMENT]) when the walk completes,
+ * t.identity when the source is resolved. */
+typedef struct {
+  cg_l4_tuple t;
+  uint16_t lxc_id;
+  uint8_t family; /* 0, 4 or 6 */
+  uint8_t pad;
+} cg_l4_frame_info;
+int cg_l4_frames_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
+                              const uint64_t* d_raw_off, size_t n, const uint16_t* d_lxc_ids, uint32_t ep_id,
+                              const uint32_t* d_src_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
+                              int32_t* d_verdicts, cg_l4_frame_info* d_info /* may be NULL */, void* stream);
+int cg_l4_frames_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                               const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
+                               const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                               int32_t* verdicts, cg_l4_frame_info* info /* may be NULL */);
+
 /* ======================================================================== */
 /* LPM: XDP CIDR prefilter — bpf/bpf_xdp.c:88-184,                           */
 /* pkg/datapath/prefilter/prefilter.go:57-298                                */
@@ -965,6 +1078,14 @@ int cg_diag_l4_eval_host(uint64_t h, uint32_t map_id, const cg_l4_tuple* tuples,
  * them, with `mode` applied (no counters). */
 int cg_diag_l4_array_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint16_t* lxc_ids,
                                const cg_l4_tuple* tuples, size_t n, int32_t* verdicts);
+/* cg_l4_frames_verdicts_* on the host: the kernel's own walk (frame_walk.h,
+ * l4_walk.h) over the host copies of the tables.  Needs no device and moves
+ * no counters.  l4_off (may be NULL): the L4 offset the walk found per frame,
+ * 0 where it did not get that far. */
+int cg_diag_l4_frames_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
+                                const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                int32_t* verdicts, cg_l4_frame_info* info, uint32_t* l4_off);
 /* The ipcache tables walked on the host exactly as ipcache_kernel does. */
 int cg_diag_ipcache_eval_host(uint64_t h, uint32_t ipc_id, const uint32_t* v4, size_t n4,
                               cg_remote_endpoint_info* out4, const uint8_t* v6, size_t n6,

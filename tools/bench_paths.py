@@ -19,6 +19,10 @@ configs, one JSON line each (bench.py covers config 5, the 10K-rule HTTP set):
   config 2's table mix, 100M tuples that each name their endpoint, against
   the per-map route (pre-grouped launches; sort + launches + scatter from
   host data) and the single-map figure
+* l4_frames (opt-in, --paths l4_frames): L4 verdicts from raw Ethernet frames
+  — 2^24 frames snapped to 96 B over 256 endpoints, endpoint and source
+  identity resolved on the device — against the tuple route on pre-extracted
+  tuples and against host extraction + upload + that route
 
 Inputs are resident in HBM before timing; kernels are timed with HIP events
 on their stream.  Each line carries the kernel's HBM roofline (algorithmic
@@ -284,6 +288,168 @@ def bench_l4_array(torch, dev, stream, cl, args, threads):
                 {"config": {"workload": "256 policy maps of config 2's 16,384-entry mix, config 2's tuples",
                             "maps": E, "distinct_tuples": D, "tuples": n},
                  "mixes": res, "single_map_ceiling_Gtuples_s": ceiling["value"] / 1e9})
+
+
+def bench_l4_frames(torch, dev, stream, cl, args, threads):
+    """L4 verdicts from raw frames: 256 endpoints' maps (config 2's table mix)
+    behind an endpoint map, a 64K-entry ipcache, Ethernet frames snapped to 96
+    bytes (about 80% IPv4 TCP/UDP, 15% IPv6 with a twentieth of those carrying
+    extension headers, 5% ICMP, other protocols, non-IP or truncated), tiled to
+    2^24 on the device.  Checked against cg_diag_l4_frames_eval_host over the
+    first copy before timing.  Beside the frames kernel, on the same packets:
+    (a) cg_l4_array_verdicts_ipcache_dev over the tuples extracted beforehand
+    (the frames whose walk completes, one call per family): strictly less
+    work, a ceiling; (b) what a caller does without this path, from host
+    data: header extraction on the host (numpy over the plain IPv4 and IPv6
+    frames; the few with extension headers are left out of its timing),
+    upload, those calls, download — against blob upload, one call, download."""
+    from cilium_amd import _native as N
+    from cilium_amd import synth
+    from cilium_amd.classifier import FRAME_INFO_DTYPE, L4_TUPLE_DTYPE
+    E, D, n = 256, args.frames, 1 << 24
+    reps = max(1, n // D)
+    n = D * reps
+    rng = np.random.default_rng(0xF4A5)
+    maps, tports = [], []
+    for e in range(E):
+        keys, ports = _l4_table_mix(np.random.default_rng(1000 + e))
+        pm = cl.policy_map()
+        pm.allow_keys(keys, ports)
+        maps.append(pm)
+        tports.append(keys["dport"][keys["dport"] != 0][:4096])
+    slots = (np.arange(E) * 257).astype(np.uint16)
+    arr = cl.policy_array()
+    arr.set_many(slots, maps)
+    ep4 = np.stack([np.full(E, 10), np.full(E, 200), np.arange(E) >> 4, np.arange(E) & 15], 1).astype(np.uint8)
+    ep6 = np.zeros((E, 16), np.uint8)
+    ep6[:, 0], ep6[:, 15] = 0xfd, np.arange(E)
+    ep = cl.endpoint_map()
+    ep.write_endpoints([".".join(map(str, a)) for a in ep4], slots)
+    ep.write_endpoints(["fd00::%x" % e if e else "fd00::" for e in range(E)], slots)
+    ik, iv = synth.ipcache_entries(65536, n_nodes=512)
+    iv = iv.copy()
+    iv[:, 0] = np.where(iv[:, 0] == 0, 0, 256 + rng.integers(0, 16384, len(iv)))
+    ipc = cl.ipcache()
+    ipc.update(ik, iv)
+    s4, s6 = synth.ipcache_addresses(8192, ik, seed=9)
+    chunks = [synth.l4_frames(D // 4, ep4, ep6, s4.view(np.uint8).reshape(-1, 4), s6, np.concatenate(tports),
+                              seed=100 + c, min_len=64, max_len=1500, snap=96) for c in range(4)]
+    raw = np.concatenate([c[0] for c in chunks])
+    lens = np.concatenate([np.diff(c[1].astype(np.int64)) for c in chunks])
+    off = np.zeros(D + 1, np.uint64)
+    np.cumsum(lens, out=off[1:])
+    plen = np.concatenate([c[2] for c in chunks])
+    blob = len(raw)
+    d_raw = tile_dev(torch, raw, reps, dev)
+    d_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    d_off[:D + 1].copy_(torch.from_numpy(off.view(np.int64)))
+    for r in range(1, reps):
+        d_off[r * D + 1:(r + 1) * D + 1].copy_(d_off[1:D + 1] + r * blob)
+    d_len = tile_dev(torch, plen, reps, dev).view(torch.int32)
+    d_out = torch.empty(n, dtype=torch.int32, device=dev)
+    d_info = torch.empty((D, 16), dtype=torch.uint8, device=dev)
+    kw = dict(endpoints=ep, ipcache=ipc)
+    arr.frame_verdicts_dev(d_raw, d_off, D, d_out, d_pkt_len=d_len, d_info=d_info, stream=stream.cuda_stream, **kw)
+    stream.synchronize()
+    t0 = time.perf_counter()
+    want, winfo = arr.frame_eval_host_diag(raw, off, pkt_len=plen, info=True, **kw)
+    cpu = D / (time.perf_counter() - t0)
+    assert np.array_equal(d_out[:D].cpu().numpy(), want), "frame verdicts differ from the host evaluator"
+    assert np.array_equal(d_info.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1), winfo), "frame info differs"
+    del d_info
+    sec = timed(torch, stream, lambda: arr.frame_verdicts_dev(d_raw, d_off, n, d_out, d_pkt_len=d_len,
+                                                              stream=stream.cuda_stream, **kw), args.steps, 2)
+    # (a) the tuple route over pre-extracted tuples, kernels only
+    ran = winfo["t"]["flags"] != 0
+    fam4 = ran & (winfo["family"] == 4)
+    fam6 = ran & (winfo["family"] == 6)
+    start = off[:-1].astype(np.int64)
+    sa4 = raw[start[fam4][:, None] + np.arange(26, 30)].copy().view(np.uint32).reshape(-1)
+    sa6 = raw[start[fam6][:, None] + np.arange(22, 38)].copy()
+    calls = []
+    for fam, sel, addrs in ((4, fam4, sa4), (6, fam6, sa6)):
+        m = int(sel.sum())
+        d_a = tile_dev(torch, addrs, reps, dev)
+        d_t = tile_dev(torch, np.ascontiguousarray(winfo["t"][sel]), reps, dev)
+        d_l = tile_dev(torch, np.ascontiguousarray(winfo["lxc_id"][sel]), reps, dev).view(torch.int16)
+        d_o = torch.empty(m * reps, dtype=torch.int32, device=dev)
+        arr.verdicts_via_ipcache_dev(ipc, fam, d_a, d_l, d_t, m, d_o, stream=stream.cuda_stream, mode=N.CG_L4_INGRESS)
+        stream.synchronize()
+        assert np.array_equal(d_o[:m].cpu().numpy(), want[sel]), "the tuple route differs on the extracted tuples"
+        calls.append((fam, d_a, d_l, d_t, m * reps, d_o))
+
+    def tuple_route():
+        for fam, d_a, d_l, d_t, m, d_o in calls:
+            arr.verdicts_via_ipcache_dev(ipc, fam, d_a, d_l, d_t, m, d_o, stream=stream.cuda_stream,
+                                         mode=N.CG_L4_INGRESS)
+    sec_a = timed(torch, stream, tuple_route, args.steps, 2)
+    n_a = sum(c[4] for c in calls)
+    del calls
+    # (b) from host data, D frames: host extraction + upload + the tuple calls + download, against the frames call
+    lut = {bytes(a): s for a, s in zip(ep4, slots)}
+    lut.update({bytes(a): s for a, s in zip(ep6, slots)})
+
+    def extract():
+        et = raw[np.minimum(start + 12, blob - 1)].astype(np.uint16) << 8 | raw[np.minimum(start + 13, blob - 1)]
+        out = []
+        for fam, code, amin in ((4, 0x0800, 34), (6, 0x86DD, 54)):
+            idx = np.flatnonzero((et == code) & (lens >= amin + 14))
+            b = start[idx]
+            if fam == 4:
+                l4 = 14 + (raw[b + 14] & 0xF).astype(np.int64) * 4
+                proto, frag = raw[b + 23], ((raw[b + 20] & 0xBF) | raw[b + 21]) != 0
+                sa = raw[b[:, None] + np.arange(26, 30)].copy().view(np.uint32).reshape(-1)
+                da = raw[b[:, None] + np.arange(30, 34)]
+            else:
+                l4 = np.full(len(idx), 54, np.int64)
+                proto, frag = raw[b + 20], np.zeros(len(idx), bool)
+                sa = raw[b[:, None] + np.arange(22, 38)].copy()
+                da = raw[b[:, None] + np.arange(38, 54)]
+            ok = np.isin(proto, (6, 17)) & (l4 + 14 <= lens[idx])
+            idx, b, l4, sa, da = idx[ok], b[ok], l4[ok], sa[ok], da[ok]
+            t = np.zeros(len(idx), L4_TUPLE_DTYPE)
+            t["dport"] = raw[b + l4 + 2].astype(np.uint16) | raw[b + l4 + 3].astype(np.uint16) << 8
+            t["proto"], t["flags"], t["len"] = proto[ok], 1 | frag[ok].astype(np.uint8) << 1, plen[idx]
+            key = da.view(f"V{da.shape[1]}").reshape(-1)
+            uniq, inv = np.unique(key, return_inverse=True)
+            lx = np.array([lut.get(u.tobytes(), 1) for u in uniq], np.uint16)[inv]  # slot 1 is empty
+            out.append((fam, idx, sa, lx, t))
+        return out
+
+    t0 = time.perf_counter()
+    parts = extract()
+    t_extract = time.perf_counter() - t0
+    back = np.full(D, 0, np.int32)
+    for fam, idx, sa, lx, t in parts:
+        dd = [torch.from_numpy(x.view(np.uint8).reshape(-1)).to(dev) for x in (sa, lx, t)]
+        dd_o = torch.empty(len(idx), dtype=torch.int32, device=dev)
+        arr.verdicts_via_ipcache_dev(ipc, fam, dd[0], dd[1], dd[2], len(idx), dd_o, stream=stream.cuda_stream,
+                                     mode=N.CG_L4_INGRESS)
+        stream.synchronize()
+        back[idx] = dd_o.cpu().numpy()
+    wall_b = time.perf_counter() - t0
+    plain = np.concatenate([p[1] for p in parts])
+    local = want[plain] != N.CG_FRAME_NOT_LOCAL
+    assert np.array_equal(back[plain][local], want[plain][local]), "host extraction differs from the frames path"
+    t0 = time.perf_counter()
+    dd = [torch.from_numpy(x).to(dev) for x in (raw, off.view(np.int64), plen.view(np.int32))]
+    dd_o = torch.empty(D, dtype=torch.int32, device=dev)
+    arr.frame_verdicts_dev(dd[0], dd[1], D, dd_o, d_pkt_len=dd[2], stream=stream.cuda_stream, **kw)
+    stream.synchronize()
+    dd_o.cpu().numpy()
+    wall_f = time.perf_counter() - t0
+    per_frame = blob / D + 8 + 4
+    return line("L4 verdicts/s from raw frames across 256 endpoints (l4_frames_kernel: header walk, endpoint map, "
+                "ipcache, policy program array)", n, sec, per_frame + 4, "l4_frames_kernel", cpu,
+                "cg_diag_l4_frames_eval_host over the first copy, one thread", 1,
+                {"config": {"workload": "256 policy maps of config 2's mix, frames snapped to 96 B", "maps": E,
+                            "distinct_frames": D, "frames": n, "blob_bytes_per_frame": blob / D,
+                            "policy_verdict_frac": float(ran.mean()), "allowed_frac": float((want >= 0).mean())},
+                 "kernel_ms": sec * 1e3, "Gframes_s": n / sec / 1e9,
+                 "algorithmic_bytes_per_frame_in": per_frame,
+                 "tuple_route_ceiling": {"kernel_ms": sec_a * 1e3, "tuples": n_a, "Gtuples_s": n_a / sec_a / 1e9},
+                 "from_host_data": {"frames": D, "host_extract_s": t_extract, "tuple_route_wall_s": wall_b,
+                                    "frames_wall_s": wall_f, "frames_left_unparsed": int(D - len(plain))}})
 
 
 def bench_lpm(torch, dev, stream, cl, args, threads):
@@ -1182,6 +1348,7 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=5.0)
     ap.add_argument("--prewarm-seconds", type=float, default=0.3)
     ap.add_argument("--array-tuples", type=int, default=1 << 26, help="l4_array: distinct tuples before tiling")
+    ap.add_argument("--frames", type=int, default=1 << 22, help="l4_frames: distinct frames before tiling to 2^24")
     args = ap.parse_args()
     global PREWARM_S
     PREWARM_S = args.prewarm_seconds
@@ -1195,7 +1362,7 @@ def main():
            "proxylib": bench_proxylib, "l4ipc": bench_l4ipc, "kafkawire": bench_kafka_wire, "httphost": bench_http_host, "httpraw": bench_http_raw,
            "httpfields": bench_http_fields, "memcache": bench_memcache, "cassandra": bench_cassandra,
            "kafkawirez": lambda *a: bench_kafka_wire(*a, codec_frac=0.5), "selcache": bench_selcache,
-           "selcache_cidr": bench_selcache_cidr, "l4_array": bench_l4_array}
+           "selcache_cidr": bench_selcache_cidr, "l4_array": bench_l4_array, "l4_frames": bench_l4_frames}
     for p in args.paths.split(","):
         print(json.dumps(fns[p](torch, dev, stream, cl, args, threads)), flush=True)
     cl.close()
