@@ -165,6 +165,7 @@ SIGNATURES = {
     "cg_http_policy_index": (C.c_int, [_u64, C.c_char_p, C.POINTER(_u32)]),
     "cg_http_policy_stats": (C.c_int, [_u64, C.POINTER(_u64), _sz]),
     "cg_http_rule_info_get": (C.c_int, [_u64, _p, _sz, C.POINTER(_sz)]),
+    "cg_diag_http_tokens": (C.c_int, [_u64, _u32, _p, _p, _sz, C.POINTER(_sz)]),
     "cg_http_batch_bytes": (_sz, [_u64, _sz]),
     "cg_http_batch_slots": (_sz, [_u64, _sz]),
     "cg_http_pack": (C.c_int, [_u64, _sz, _p, _p, _p, _p, _p, _p, _p, _sz, _p, C.POINTER(_sz), _p, _sz,

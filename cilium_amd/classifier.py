@@ -156,10 +156,10 @@ class Classifier:
         return v.value
 
     def http_policy_stats(self) -> dict:
-        out = (C.c_uint64 * 12)()
-        N.check(N.lib.cg_http_policy_stats(self.h, out, 12))
+        out = (C.c_uint64 * 14)()
+        N.check(N.lib.cg_http_policy_stats(self.h, out, 14))
         keys = ["programs", "parts", "states", "table_bytes", "fields", "rules", "policies", "remote_slots",
-                "exceptions", "cells", "max_program_cells", "lds_programs"]
+                "exceptions", "cells", "max_program_cells", "lds_programs", "tokens", "token_cells"]
         return dict(zip(keys, list(out)))
 
     def pack_http(self, policy: np.ndarray, ingress: np.ndarray, port: np.ndarray, remote: np.ndarray,
@@ -335,6 +335,21 @@ class Classifier:
         N.check(N.lib.cg_diag_http_rules_host(self.h, _p(b.batch), b.nslots, _p(b.order), b.n, _p(b.arena),
                                               b.arena.nbytes, _p(out)))
         return out[:b.n]
+
+    def http_tokens_diag(self, prog: int) -> tuple[np.ndarray, list[tuple[int, bytes]]]:
+        """Compiler diagnostics only: program `prog`'s byte → code map and its
+        literal tokens as (token code, class-code sequence)."""
+        code_map = np.zeros(256, np.uint8)
+        used = C.c_size_t()
+        N.check(N.lib.cg_diag_http_tokens(self.h, prog, _p(code_map), None, 0, C.byref(used)))
+        buf = np.zeros(max(used.value, 1), np.uint8)
+        N.check(N.lib.cg_diag_http_tokens(self.h, prog, None, _p(buf), buf.nbytes, C.byref(used)))
+        toks, at = [], 0
+        while at < used.value:
+            n = int(buf[at + 1])
+            toks.append((int(buf[at]), buf[at + 2:at + 2 + n].tobytes()))
+            at += 2 + n
+        return code_map, toks
 
     def http_eval_host_diag_slots(self, b: "HttpBatch") -> np.ndarray:
         """Compiler diagnostics only: the host walk's verdict per batch slot."""

@@ -1774,7 +1774,7 @@ int cg_http_policy_stats(uint64_t h, uint64_t* out, size_t n) {
       max_prog_cells = std::max<uint64_t>(max_prog_cells, pg.cell_count);
       lds_progs += (pg.flags & kProgRebased) && pg.cell_count <= kMaxLdsCells;
     }
-    uint64_t v[12] = {s->progs.size(),
+    uint64_t v[14] = {s->progs.size(),
                      s->parts.size(),
                      s->total_states,
                      s->cells.size() * 4,
@@ -1785,8 +1785,31 @@ int cg_http_policy_stats(uint64_t h, uint64_t* out, size_t n) {
                      s->total_exceptions,
                      s->cells.size(),
                      max_prog_cells,
-                     lds_progs};
-    for (size_t i = 0; i < n && i < 12; ++i) out[i] = v[i];
+                     lds_progs,
+                     s->total_tokens,
+                     s->total_token_cells};
+    for (size_t i = 0; i < n && i < 14; ++i) out[i] = v[i];
+  });
+}
+
+int cg_diag_http_tokens(uint64_t h, uint32_t prog, uint8_t* code_map, uint8_t* out, size_t cap, size_t* used) {
+  return guarded([&] {
+    auto e = get(h);
+    auto s = http_snap(*e);
+    if (prog >= s->progs.size()) fail(CG_INVALID_ARGUMENT, "no such HTTP program");
+    const bool cls = s->progs[prog].flags & kProgClass;
+    if (code_map)
+      for (int b = 0; b < 256; ++b) code_map[b] = cls ? s->prog_code[prog][b] : (uint8_t)b;
+    size_t at = 0;
+    for (const auto& t : s->prog_tokens[prog]) {
+      if (out && at + 2 + t.seq.size() <= cap) {
+        out[at] = t.code;
+        out[at + 1] = (uint8_t)t.seq.size();
+        memcpy(out + at + 2, t.seq.data(), t.seq.size());
+      }
+      at += 2 + t.seq.size();
+    }
+    if (used) *used = at;
   });
 }
 

@@ -203,6 +203,11 @@ constexpr uint32_t kLdsRuleHits = 512;
 // instantiation stages after the block): the largest program table a
 // workgroup stages (http.cc, http_pack.cc)
 constexpr uint32_t kMaxLdsCells = (160 * 1024 - 64 - 4 * kLdsRuleHits - 4 * 64) / 4;
+// The largest program block with which two http_kernel workgroups still share
+// a CU's 160 KiB (80 KiB each: the block rounded up to 256 cells as
+// HttpDev.lds_cells is, the code map, the rule hits and the counter words).
+// Literal-token columns (clsdfa.h) may grow a block up to here, never past it.
+constexpr uint32_t kTwoWgLdsCells = (80 * 1024 / 4 - 64 - kLdsRuleHits - 3) & ~255u;
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;  // empty remote-table slot
 // One DFA of a program as a comb-packed table (comb.h).  A state is its base
 // cell index relative to `walk_off`; `dead` is the dead state, states above it

@@ -697,148 +697,211 @@ std::shared_ptr<HttpSnapshot> http_compile(const char* json, size_t len) {
       S.prog_code.resize(pid + 1);
       S.prog_code[pid] = code;
     }
-    pg.part_begin = (uint32_t)S.parts.size();
-    pg.part_count = (uint32_t)parts.size();
-    while (S.cells.size() & 3) S.cells.push_back(kCombEmpty);  // blocks start 16-byte aligned
-    pg.cell_begin = (uint32_t)S.cells.size();
-    size_t block = 0;
-    for (const auto& po : parts) block += po.comb.cells.size();
-    const bool rebase = block <= kCombMaxBase;
-    if (rebase) pg.flags |= kProgRebased;
-    for (auto& po : parts) {
-      HttpPart hp{};
-      const ClsDfa& d = po.dfa;
-      CombTable& cb = po.comb;
-      hp.cell_off = (uint32_t)S.cells.size();
-      if (rebase) rebase_comb(&cb, hp.cell_off - pg.cell_begin);
-      hp.walk_off = rebase ? pg.cell_begin : hp.cell_off;
-      hp.nstates = (uint32_t)d.size();
-      hp.start = cb.start;
-      hp.dead = cb.dead;
-      hp.ncells = (uint32_t)cb.cells.size();
-      hp.mode = cb.scaled ? kPartClass : 0;
-      S.cells.insert(S.cells.end(), cb.cells.begin(), cb.cells.end());
-      S.total_states += d.size();
-      S.total_exceptions += cb.exceptions;
-      S.parts.push_back(hp);
-    }
-    // The block continues with each part's label masks (indexed by accept
-    // label) and the "always" mask, masks as 8-byte-aligned u64 pairs at
-    // block-relative u32 offsets: the kernel stages the whole block into LDS
-    // with the DFA.
-    auto put_mask = [&](const std::vector<uint64_t>& m) -> uint32_t {
-      if (S.cells.size() & 1) S.cells.push_back(0);
-      const uint32_t off = (uint32_t)S.cells.size() - pg.cell_begin;
-      for (uint64_t w : m) {
-        S.cells.push_back((uint32_t)w);
-        S.cells.push_back((uint32_t)(w >> 32));
-      }
-      return off;
+    // emit() appends the program's parts and block to the snapshot and fills
+    // pg; retract() takes that back, so the block can be laid out again with
+    // another table (the token columns below)
+    const size_t parts0 = S.parts.size(), cells0 = S.cells.size();
+    const uint64_t totals0[3] = {S.total_states, S.total_exceptions, S.total_remote_slots};
+    const HttpProg pg0 = pg;
+    auto retract = [&] {
+      S.parts.resize(parts0);
+      S.cells.resize(cells0);
+      S.total_states = totals0[0];
+      S.total_exceptions = totals0[1];
+      S.total_remote_slots = totals0[2];
+      pg = pg0;
     };
-    // each part's label masks back to back (stride 2W u32): accept label l of
-    // part i has its PNPR mask at block offset acc_off + l * 2W
-    for (size_t i = 0; i < parts.size(); ++i) {
-      HttpPart& hp = S.parts[pg.part_begin + i];
-      if (S.cells.size() & 1) S.cells.push_back(0);
-      hp.acc_off = (uint32_t)S.cells.size() - pg.cell_begin;
-      for (size_t l = 0; l < parts[i].label_masks.size(); ++l) put_mask(parts[i].label_masks[l]);
-    }
-    pg.always_off = put_mask(always);
-    // remote-identity table (PortNetworkPolicyRule remote sets, :90-97):
-    // identity → block offset of its rule mask row (rows deduplicated;
-    // dev_types.h rtab_b1/rtab_b2 buckets); unlisted identities get the row
-    // of the rules without a remote set
-    {
-      std::map<std::vector<uint64_t>, uint32_t> rows;
-      auto row_of = [&](const std::vector<uint64_t>& m) {
-        auto it = rows.find(m);
-        if (it == rows.end()) it = rows.emplace(m, put_mask(m)).first;
-        return it->second;
+    auto emit = [&] {
+      pg.part_begin = (uint32_t)S.parts.size();
+      pg.part_count = (uint32_t)parts.size();
+      while (S.cells.size() & 3) S.cells.push_back(kCombEmpty);  // blocks start 16-byte aligned
+      pg.cell_begin = (uint32_t)S.cells.size();
+      size_t block = 0;
+      for (const auto& po : parts) block += po.comb.cells.size();
+      const bool rebase = block <= kCombMaxBase;
+      if (rebase) pg.flags |= kProgRebased;
+      for (auto& po : parts) {
+        HttpPart hp{};
+        const ClsDfa& d = po.dfa;
+        CombTable& cb = po.comb;
+        hp.cell_off = (uint32_t)S.cells.size();
+        if (rebase) rebase_comb(&cb, hp.cell_off - pg.cell_begin);
+        hp.walk_off = rebase ? pg.cell_begin : hp.cell_off;
+        hp.nstates = (uint32_t)d.size();
+        hp.start = cb.start;
+        hp.dead = cb.dead;
+        hp.ncells = (uint32_t)cb.cells.size();
+        hp.mode = cb.scaled ? kPartClass : 0;
+        S.cells.insert(S.cells.end(), cb.cells.begin(), cb.cells.end());
+        S.total_states += d.size();
+        S.total_exceptions += cb.exceptions;
+        S.parts.push_back(hp);
+      }
+      // The block continues with each part's label masks (indexed by accept
+      // label) and the "always" mask, masks as 8-byte-aligned u64 pairs at
+      // block-relative u32 offsets: the kernel stages the whole block into LDS
+      // with the DFA.
+      auto put_mask = [&](const std::vector<uint64_t>& m) -> uint32_t {
+        if (S.cells.size() & 1) S.cells.push_back(0);
+        const uint32_t off = (uint32_t)S.cells.size() - pg.cell_begin;
+        for (uint64_t w : m) {
+          S.cells.push_back((uint32_t)w);
+          S.cells.push_back((uint32_t)(w >> 32));
+        }
+        return off;
       };
-      pg.default_remote = row_of(open);
-      std::vector<std::pair<uint32_t, uint32_t>> ent;
-      for (auto& [rid, m] : by_remote) ent.push_back({rid, row_of(m)});
-      // 2-choice cuckoo placement into the fewest buckets that take it
-      uint32_t nb = (uint32_t)std::max<size_t>((ent.size() * 10 / 9 + 3) / 4, 1);
-      std::vector<std::pair<uint32_t, uint32_t>> slots;  // (identity, row) per slot, row kNoRow = empty
-      for (;; nb += nb / 8 + 1) {
-        if (nb >= 65536) fail(CG_POLICY_REJECTED, "too many remote identities in one HTTP policy scope");
-        slots.assign((size_t)nb * 4, {0u, kNoRow});
-        std::mt19937 rng(0xC111A);
-        auto put = [&](uint32_t bk, const std::pair<uint32_t, uint32_t>& e) {
-          for (int sl = 0; sl < 4; ++sl)
-            if (slots[(size_t)bk * 4 + sl].second == kNoRow) {
-              slots[(size_t)bk * 4 + sl] = e;
-              return true;
-            }
-          return false;
+      // each part's label masks back to back (stride 2W u32): accept label l of
+      // part i has its PNPR mask at block offset acc_off + l * 2W
+      for (size_t i = 0; i < parts.size(); ++i) {
+        HttpPart& hp = S.parts[pg.part_begin + i];
+        if (S.cells.size() & 1) S.cells.push_back(0);
+        hp.acc_off = (uint32_t)S.cells.size() - pg.cell_begin;
+        for (size_t l = 0; l < parts[i].label_masks.size(); ++l) put_mask(parts[i].label_masks[l]);
+      }
+      pg.always_off = put_mask(always);
+      // remote-identity table (PortNetworkPolicyRule remote sets, :90-97):
+      // identity → block offset of its rule mask row (rows deduplicated;
+      // dev_types.h rtab_b1/rtab_b2 buckets); unlisted identities get the row
+      // of the rules without a remote set
+      {
+        std::map<std::vector<uint64_t>, uint32_t> rows;
+        auto row_of = [&](const std::vector<uint64_t>& m) {
+          auto it = rows.find(m);
+          if (it == rows.end()) it = rows.emplace(m, put_mask(m)).first;
+          return it->second;
         };
-        bool ok = true;
-        for (const auto& e : ent) {
-          auto cur = e;
-          uint32_t from = 0xFFFFFFFFu;
-          bool placed = false;
-          for (int kick = 0; kick < 500 && !placed; ++kick) {
-            const uint32_t c1 = rtab_b1(cur.first, nb), c2 = rtab_b2(cur.first, nb);
-            if (put(c1, cur) || put(c2, cur)) {
-              placed = true;
+        pg.default_remote = row_of(open);
+        std::vector<std::pair<uint32_t, uint32_t>> ent;
+        for (auto& [rid, m] : by_remote) ent.push_back({rid, row_of(m)});
+        // 2-choice cuckoo placement into the fewest buckets that take it
+        uint32_t nb = (uint32_t)std::max<size_t>((ent.size() * 10 / 9 + 3) / 4, 1);
+        std::vector<std::pair<uint32_t, uint32_t>> slots;  // (identity, row) per slot, row kNoRow = empty
+        for (;; nb += nb / 8 + 1) {
+          if (nb >= 65536) fail(CG_POLICY_REJECTED, "too many remote identities in one HTTP policy scope");
+          slots.assign((size_t)nb * 4, {0u, kNoRow});
+          std::mt19937 rng(0xC111A);
+          auto put = [&](uint32_t bk, const std::pair<uint32_t, uint32_t>& e) {
+            for (int sl = 0; sl < 4; ++sl)
+              if (slots[(size_t)bk * 4 + sl].second == kNoRow) {
+                slots[(size_t)bk * 4 + sl] = e;
+                return true;
+              }
+            return false;
+          };
+          bool ok = true;
+          for (const auto& e : ent) {
+            auto cur = e;
+            uint32_t from = 0xFFFFFFFFu;
+            bool placed = false;
+            for (int kick = 0; kick < 500 && !placed; ++kick) {
+              const uint32_t c1 = rtab_b1(cur.first, nb), c2 = rtab_b2(cur.first, nb);
+              if (put(c1, cur) || put(c2, cur)) {
+                placed = true;
+                break;
+              }
+              // evict from the bucket the current entry did not come from
+              const uint32_t vb = c1 == from ? c2 : c2 == from ? c1 : (rng() & 1) ? c1 : c2;
+              std::swap(cur, slots[(size_t)vb * 4 + (rng() & 3)]);
+              from = vb;
+            }
+            if (!placed) {
+              ok = false;
               break;
             }
-            // evict from the bucket the current entry did not come from
-            const uint32_t vb = c1 == from ? c2 : c2 == from ? c1 : (rng() & 1) ? c1 : c2;
-            std::swap(cur, slots[(size_t)vb * 4 + (rng() & 3)]);
-            from = vb;
           }
-          if (!placed) {
-            ok = false;
-            break;
-          }
+          if (ok) break;
         }
-        if (ok) break;
-      }
-      while ((S.cells.size() - pg.cell_begin) & 3) S.cells.push_back(0);  // buckets 16-byte aligned
+        while ((S.cells.size() - pg.cell_begin) & 3) S.cells.push_back(0);  // buckets 16-byte aligned
 
-      pg.rtab_off = (uint32_t)S.cells.size() - pg.cell_begin;
-      pg.rtab_nb = nb;
-      // empty slots: an identity the table does not hold, with the default row
-      uint32_t empty_id = 0;
-      while (by_remote.count(empty_id)) ++empty_id;
-      const size_t at = S.cells.size();
-      S.cells.resize(at + kRtabBucketCells * (size_t)nb, 0);
-      for (uint32_t k = 0; k < nb; ++k)
-        for (int sl = 0; sl < 4; ++sl) {
-          const auto& e = slots[(size_t)k * 4 + sl];
-          const bool empty = e.second == kNoRow;
-          S.cells[at + kRtabBucketCells * k + sl] = empty ? empty_id : e.first;
-          S.cells[at + kRtabBucketCells * k + 4 + sl] = empty ? pg.default_remote : e.second;
-        }
-      const uint32_t cap = 4 * nb;
-      S.total_remote_slots += cap;
-      // identities over a short span (identities are allocated densely): a
-      // direct u16 row array as well, which the kernel prefers
-      if (!ent.empty()) {
-        uint32_t lo = ent[0].first, hi = ent[0].first;
-        bool rows16 = pg.default_remote < 0x10000;
-        for (const auto& e : ent) {
-          lo = std::min(lo, e.first);
-          hi = std::max(hi, e.first);
-          rows16 &= e.second < 0x10000;
-        }
-        if (rows16 && hi - lo < kRdirMaxSpan) {
-          const uint32_t len = hi - lo + 1;
-          std::vector<uint16_t> t(len + 1, (uint16_t)pg.default_remote);
-          for (const auto& e : ent) t[e.first - lo] = (uint16_t)e.second;
-          pg.rdir_base = lo;
-          pg.rdir_len = len;
-          pg.rdir_off = (uint32_t)S.cells.size() - pg.cell_begin;
-          for (uint32_t k = 0; k < len; k += 2) S.cells.push_back((uint32_t)t[k] | (uint32_t)t[k + 1] << 16);
-          pg.flags |= kProgRemoteDirect;
+        pg.rtab_off = (uint32_t)S.cells.size() - pg.cell_begin;
+        pg.rtab_nb = nb;
+        // empty slots: an identity the table does not hold, with the default row
+        uint32_t empty_id = 0;
+        while (by_remote.count(empty_id)) ++empty_id;
+        const size_t at = S.cells.size();
+        S.cells.resize(at + kRtabBucketCells * (size_t)nb, 0);
+        for (uint32_t k = 0; k < nb; ++k)
+          for (int sl = 0; sl < 4; ++sl) {
+            const auto& e = slots[(size_t)k * 4 + sl];
+            const bool empty = e.second == kNoRow;
+            S.cells[at + kRtabBucketCells * k + sl] = empty ? empty_id : e.first;
+            S.cells[at + kRtabBucketCells * k + 4 + sl] = empty ? pg.default_remote : e.second;
+          }
+        const uint32_t cap = 4 * nb;
+        S.total_remote_slots += cap;
+        // identities over a short span (identities are allocated densely): a
+        // direct u16 row array as well, which the kernel prefers
+        if (!ent.empty()) {
+          uint32_t lo = ent[0].first, hi = ent[0].first;
+          bool rows16 = pg.default_remote < 0x10000;
+          for (const auto& e : ent) {
+            lo = std::min(lo, e.first);
+            hi = std::max(hi, e.first);
+            rows16 &= e.second < 0x10000;
+          }
+          if (rows16 && hi - lo < kRdirMaxSpan) {
+            const uint32_t len = hi - lo + 1;
+            std::vector<uint16_t> t(len + 1, (uint16_t)pg.default_remote);
+            for (const auto& e : ent) t[e.first - lo] = (uint16_t)e.second;
+            pg.rdir_base = lo;
+            pg.rdir_len = len;
+            pg.rdir_off = (uint32_t)S.cells.size() - pg.cell_begin;
+            for (uint32_t k = 0; k < len; k += 2) S.cells.push_back((uint32_t)t[k] | (uint32_t)t[k + 1] << 16);
+            pg.flags |= kProgRemoteDirect;
+          }
         }
       }
+      S.cells.push_back(0);  // spare words: the kernel reads two mask words whatever the width
+      S.cells.push_back(0);
+      pg.cell_count = (uint32_t)S.cells.size() - pg.cell_begin;
+    };
+    emit();
+    // Literal tokens: the class codes the byte classes leave free each stand
+    // for one literal of the program's rules (clsdfa.h pick_tokens), as one
+    // more column of the table.  The block must stay LDS resident and two
+    // workgroups must still share a CU: a block that fits kTwoWgLdsCells
+    // without tokens stays within it, any other within kMaxLdsCells.
+    // pick_tokens keeps to that budget by the cells it expects a column to
+    // take; the layout decides: while it is over, the last pick goes.
+    if ((pg.flags & kProgClass) && (pg.flags & kProgRebased) && pg.cell_count <= kMaxLdsCells &&
+        parts[0].dfa.ncls < 64) {
+      const uint32_t base_count = pg.cell_count;
+      const uint32_t limit = base_count <= kTwoWgLdsCells ? kTwoWgLdsCells : kMaxLdsCells;
+      const PartOut base = parts[0];
+      const int ncls = base.dfa.ncls;
+      std::vector<uint32_t> labels(base.dfa.size(), kCombNoLabel);
+      for (int st = 0; st < base.dfa.size(); ++st)
+        if (base.dfa.label[st]) labels[st] = base.dfa.label[st] - 1;
+      std::vector<ClsSeq> toks = pick_tokens(base.dfa, base.label_masks, 64 - ncls, limit - base_count);
+      bool relaid = false;
+      while (!toks.empty()) {
+        ClsDfa wide = with_token_columns(base.dfa, toks);
+        CombTable ct;
+        if (build_comb(wide, labels, &ct, kCombMaxBase, true) && scale_comb(&ct)) {
+          retract();
+          parts[0].dfa = std::move(wide);
+          parts[0].comb = std::move(ct);
+          emit();
+          relaid = true;
+          if ((pg.flags & kProgRebased) && pg.cell_count <= limit) break;
+        }
+        toks.pop_back();  // the lowest-scoring token goes first
+      }
+      if (toks.empty() && relaid) {
+        retract();
+        parts[0] = base;
+        emit();
+      }
+      S.prog_tokens.resize(pid + 1);
+      for (size_t t = 0; t < toks.size(); ++t) {
+        HttpSnapshot::Token tk;
+        tk.code = (uint8_t)(4 * (ncls + t));
+        for (uint8_t c : toks[t]) tk.seq.push_back((uint8_t)(4 * c));
+        S.prog_tokens[pid].push_back(std::move(tk));
+      }
+      S.total_tokens += toks.size();
+      S.total_token_cells += pg.cell_count > base_count ? pg.cell_count - base_count : 0;
     }
-    S.cells.push_back(0);  // spare words: the kernel reads two mask words whatever the width
-    S.cells.push_back(0);
-    pg.cell_count = (uint32_t)S.cells.size() - pg.cell_begin;
     if (getenv("CILIUM_GPU_DEBUG")) {
       size_t comb = 0, labels = 0;
       for (uint32_t i = 0; i < pg.part_count; ++i) {
@@ -890,6 +953,7 @@ std::shared_ptr<HttpSnapshot> http_compile(const char* json, size_t len) {
   if (S.cells.empty()) S.cells.push_back(kCombEmpty);
   if (S.progs.empty()) S.progs.push_back(HttpProg{});
   S.prog_code.resize(S.progs.size());
+  S.prog_tokens.resize(S.progs.size());
   if (S.parts.empty()) S.parts.push_back(HttpPart{});
   if (S.dflt.empty()) S.dflt.push_back(kProgDeny);
   return snap;

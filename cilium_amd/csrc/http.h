@@ -30,6 +30,17 @@ struct HttpSnapshot {
   std::vector<uint32_t> prog_key;
   // class-mode programs (kProgClass): string byte b is packed as code[b]
   std::vector<std::array<uint8_t, 256>> prog_code;
+  // literal tokens of a class-mode program (clsdfa.h): the packer writes the
+  // code sequence `seq` of a string as the one symbol `code`, a column of the
+  // program's table.  No byte maps to a token code: strings of plain class
+  // codes (the device-built batches) walk to the same states.
+  struct Token {
+    uint8_t code;
+    std::vector<uint8_t> seq;  // class codes, 2..kTokenMaxLen of them
+  };
+  std::vector<std::vector<Token>> prog_tokens;
+  uint64_t total_tokens = 0;
+  uint64_t total_token_cells = 0;  // cells the token columns added to the program blocks
   // what each per-rule hit counter counts (HttpProg.rule_base + bit)
   std::vector<cg_http_rule_info> rule_info;
 

@@ -22,8 +22,12 @@ namespace cg {
 namespace {
 
 constexpr uint32_t kImageMagic = 0x49484743u;  // "CGHI"
-constexpr uint32_t kImageVersion = 1u | (uint32_t)sizeof(HttpProg) << 8 | (uint32_t)sizeof(HttpPart) << 16 |
+// version 2 adds the literal tokens (HttpSnapshot::prog_tokens) after the
+// totals; a version 1 image imports with none
+constexpr uint32_t kImageLayouts = (uint32_t)sizeof(HttpProg) << 8 | (uint32_t)sizeof(HttpPart) << 16 |
                                    (uint32_t)sizeof(cg_http_rule_info) << 24;
+constexpr uint32_t kImageVersion1 = 1u | kImageLayouts;
+constexpr uint32_t kImageVersion = 2u | kImageLayouts;
 
 uint64_t fnv64(const uint8_t* p, size_t n) {
   uint64_t h = 1469598103934665603ull;
@@ -113,6 +117,17 @@ std::vector<uint8_t> http_image_export(const HttpSnapshot& s) {
   w.u64(s.total_exceptions);
   w.u64(s.total_rules);
   w.u64(s.total_remote_slots);
+  w.u64(s.total_tokens);
+  w.u64(s.total_token_cells);
+  w.u64(s.prog_tokens.size());
+  for (const auto& toks : s.prog_tokens) {
+    w.u32((uint32_t)toks.size());
+    for (const auto& t : toks) {
+      w.u32(t.code);
+      w.u32((uint32_t)t.seq.size());
+      w.raw(t.seq.data(), t.seq.size());
+    }
+  }
   w.u64(fnv64(w.b.data(), w.b.size()));
   return std::move(w.b);
 }
@@ -132,7 +147,8 @@ void validate_image(const HttpSnapshot& s) {
     if (s.phash_keys[i] != 0xFFFFFFFFu && !prog_ref_ok(s.phash_vals[i])) bad("program hash value out of range");
   }
   if (!empty_slot) bad("program hash has no empty slot");  // lookups would probe forever
-  if (s.dflt.size() < (size_t)s.npolicies * 2 || s.prog_code.size() != np || s.prog_key.size() > np)
+  if (s.dflt.size() < (size_t)s.npolicies * 2 || s.prog_code.size() != np || s.prog_key.size() > np ||
+      s.prog_tokens.size() != np)
     bad("inconsistent tables");
   for (uint32_t v : s.dflt)
     if (!prog_ref_ok(v)) bad("default program out of range");
@@ -182,6 +198,17 @@ void validate_image(const HttpSnapshot& s) {
         if (c & 3) bad("class code not a cell offset");
         max_code = std::max<uint32_t>(max_code, c);
       }
+      // a token: a code above the class codes, for 2..kTokenMaxLen of them
+      const uint32_t max_class = max_code;
+      for (const auto& t : s.prog_tokens[pi]) {
+        if ((t.code & 3) || t.code <= max_class) bad("token code not a free cell offset");
+        if (t.seq.size() < 2 || t.seq.size() > (size_t)kTokenMaxLen) bad("bad token length");
+        for (uint8_t c : t.seq)
+          if ((c & 3) || c > max_class) bad("token symbol not a class code");
+        max_code = std::max<uint32_t>(max_code, t.code);
+      }
+    } else if (!s.prog_tokens[pi].empty()) {
+      bad("tokens of a program without class codes");
     }
     const bool rebased = pg.flags & kProgRebased;
     const uint64_t limit = rebased ? (uint64_t)pg.cell_begin + pg.cell_count : nc;
@@ -222,7 +249,9 @@ std::shared_ptr<HttpSnapshot> http_image_import(const uint8_t* p, size_t n) {
   if (sum != fnv64(p, n - 8)) fail(CG_POLICY_REJECTED, "policy image: checksum mismatch");
   Reader r{p, p + n - 8};
   if (r.u32() != kImageMagic) fail(CG_POLICY_REJECTED, "policy image: bad magic");
-  if (r.u32() != kImageVersion) fail(CG_POLICY_REJECTED, "policy image: built by another library version");
+  const uint32_t version = r.u32();
+  if (version != kImageVersion && version != kImageVersion1)
+    fail(CG_POLICY_REJECTED, "policy image: built by another library version");
   auto snap = std::make_shared<HttpSnapshot>();
   HttpSnapshot& s = *snap;
   s.raw_values = r.u32() != 0;
@@ -249,6 +278,26 @@ std::shared_ptr<HttpSnapshot> http_image_import(const uint8_t* p, size_t n) {
   s.total_exceptions = r.u64();
   s.total_rules = r.u64();
   s.total_remote_slots = r.u64();
+  if (version != kImageVersion1) {
+    s.total_tokens = r.u64();
+    s.total_token_cells = r.u64();
+    const uint64_t nprog = r.u64();
+    if (nprog > s.progs.size()) fail(CG_POLICY_REJECTED, "policy image: bad token table");
+    s.prog_tokens.resize((size_t)nprog);
+    for (auto& toks : s.prog_tokens) {
+      const uint32_t nt = r.u32();
+      if (nt > 64) fail(CG_POLICY_REJECTED, "policy image: bad token count");
+      toks.resize(nt);
+      for (auto& t : toks) {
+        t.code = (uint8_t)r.u32();
+        const uint32_t len = r.u32();
+        if (len > (uint32_t)kTokenMaxLen) fail(CG_POLICY_REJECTED, "policy image: bad token length");
+        t.seq.resize(len);
+        r.raw(t.seq.data(), len);
+      }
+    }
+  }
+  s.prog_tokens.resize(s.progs.size());
   if (r.p != r.e) fail(CG_POLICY_REJECTED, "policy image: trailing bytes");
   validate_image(s);
   s.epoch = http_next_epoch();

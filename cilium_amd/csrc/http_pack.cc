@@ -169,6 +169,28 @@ void http_pack(const HttpSnapshot& s, size_t n, const uint32_t* policy, const ui
     if (by_len.size() <= L) by_len.resize(L + 1);
     by_len[L].push_back((uint32_t)f);
   }
+  // literal tokens (HttpSnapshot::prog_tokens) by their first code: per
+  // program, tok_first[code / 4] heads a list through tok_next of the tokens
+  // that start with the code, longest first (-1 ends it).
+  // CILIUM_GPU_PACK_TOKENS=0 packs plain class codes against the same tables.
+  const char* tok_env = getenv("CILIUM_GPU_PACK_TOKENS");
+  const bool tokens = !(tok_env && tok_env[0] == '0' && !tok_env[1]);
+  std::vector<std::vector<int16_t>> tok_first(np), tok_next(np);
+  for (size_t p = 0; p < np && p < s.prog_tokens.size() && tokens && build; ++p) {
+    const auto& toks = s.prog_tokens[p];
+    if (toks.empty()) continue;
+    std::vector<int16_t> asc(toks.size());
+    for (size_t t = 0; t < toks.size(); ++t) asc[t] = (int16_t)t;
+    std::stable_sort(asc.begin(), asc.end(),
+                     [&](int16_t a, int16_t b) { return toks[a].seq.size() < toks[b].seq.size(); });
+    tok_first[p].assign(64, -1);
+    tok_next[p].assign(toks.size(), -1);
+    for (int16_t t : asc) {  // shortest first, each pushed at the head
+      int16_t& head = tok_first[p][toks[t].seq[0] >> 2];
+      tok_next[p][t] = head;
+      head = t;
+    }
+  }
   auto worker_of = [&](size_t i) -> unsigned {
     // parallel_ranges splits [0, n) at n*t/nt
     unsigned t = (unsigned)((i * nt) / n);
@@ -236,6 +258,31 @@ void http_pack(const HttpSnapshot& s, size_t n, const uint32_t* policy, const ui
       if (prog[i] < np && (s.progs[prog[i]].flags & kProgClass)) {
         const auto& code = s.prog_code[prog[i]];
         for (size_t k = o; k < strs.size(); ++k) strs[k] = code[strs[k]];
+        // literal tokens, left to right, the longest match first.  A string
+        // for the overflow arena (by its untokenized length) stays as it is.
+        if (tokens && slen[i] <= CG_HTTP_SLOT_BYTES && !tok_first[prog[i]].empty()) {
+          const auto& first = tok_first[prog[i]];
+          const auto& toks = s.prog_tokens[prog[i]];
+          uint8_t* q = strs.data() + o;
+          const size_t L = slen[i];
+          size_t w = 0;
+          for (size_t r = 0; r < L;) {
+            size_t hit = 0;
+            uint8_t sym = q[r];
+            for (int16_t t = first[q[r] >> 2]; t >= 0; t = tok_next[prog[i]][t]) {
+              const auto& sq = toks[t].seq;
+              if (sq.size() <= L - r && memcmp(q + r, sq.data(), sq.size()) == 0) {
+                hit = sq.size();
+                sym = toks[t].code;
+                break;
+              }
+            }
+            q[w++] = sym;
+            r += hit ? hit : 1;
+          }
+          strs.resize(o + w);
+          slen[i] = (uint32_t)w;
+        }
       }
     }
   });

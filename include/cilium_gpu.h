@@ -532,7 +532,9 @@ int cg_http_policy_update_npds(uint64_t h, const uint8_t* discovery_response, si
 /* Index of a policy name in the installed snapshot (for the packer);
  * CG_NOT_FOUND → requests naming it are denied (cilium_network_policy.h:232-235). */
 int cg_http_policy_index(uint64_t h, const char* name, uint32_t* index);
-/* Snapshot statistics: programs, DFA parts, total states, table bytes. */
+/* Snapshot statistics: programs, DFA parts, total states, table bytes, fields,
+ * rules, policies, remote slots, exceptions, cells, the largest program block,
+ * LDS-resident programs, literal tokens and the cells their columns added. */
 int cg_http_policy_stats(uint64_t h, uint64_t* out, size_t n);
 
 /* Per-rule hit counters (what = CG_CTR_HTTP_RULES in cg_read_counters): a
@@ -577,7 +579,12 @@ int cg_http_rule_info_get(uint64_t h, cg_http_rule_info* out, size_t cap, size_t
  * (UINT32_MAX for padding).  Size the buffers with cg_http_batch_bytes /
  * cg_http_batch_slots (upper bounds for n requests under the installed
  * policy; a batch is tied to the snapshot it was packed against — after a
- * policy update it is rejected and every slot is denied). */
+ * policy update it is rejected and every slot is denied).  A program whose
+ * strings are packed as byte-class codes spends its free codes on literals of
+ * its rules (literal tokens): cg_http_pack writes such a literal as one
+ * symbol, the program's table walks it as it walks the literal's bytes, and a
+ * string counts as longer than CG_HTTP_SLOT_BYTES by its length before that.
+ * CILIUM_GPU_PACK_TOKENS=0, read per call, packs without tokens. */
 #define CG_HTTP_TILE 64
 #define CG_HTTP_UNITS 9
 #define CG_HTTP_SLOT_BYTES 128
@@ -1061,6 +1068,13 @@ int cg_diag_regex_match(const char* re, size_t re_len, const uint8_t* s, size_t 
  * do, to test the compilers without a GPU. */
 int cg_diag_http_eval_host(uint64_t h, const void* batch, size_t nslots, const uint32_t* order,
                            size_t n, const uint8_t* arena, size_t arena_len, uint8_t* out);
+/* The literal tokens of program `prog` (its index in the per-program
+ * counters): code_map[256] receives the code the packer writes for each
+ * string byte (the byte itself for a program without class codes), out the
+ * records {token code, length, that many class codes}; *used is their size.
+ * cg_http_pack writes a token's code for its class-code sequence unless
+ * CILIUM_GPU_PACK_TOKENS=0 is set; the tables walk both to the same state. */
+int cg_diag_http_tokens(uint64_t h, uint32_t prog, uint8_t* code_map, uint8_t* out, size_t cap, size_t* used);
 /* The same walk, reporting per request the per-rule hit counter it adds to
  * (cg_http_rule_info_get index), or UINT32_MAX when no rule allows it. */
 int cg_diag_http_rules_host(uint64_t h, const void* batch, size_t nslots, const uint32_t* order,
