@@ -46,6 +46,13 @@ CG_DROP_INVALID, CG_DROP_CT_INVALID_HDR, CG_DROP_CT_UNKNOWN_PROTO, CG_DROP_UNKNO
 CG_DROP_INVALID_EXTHDR = -156
 CG_FRAME_NOT_LOCAL, CG_FRAME_TO_HOST = -1, -2
 CG_ENDPOINT_F_HOST = 1
+CG_CT_MAP_TCP, CG_CT_MAP_ANY = 0, 1
+CG_CT_MAP_F_GLOBAL = 1
+CG_TUPLE_F_OUT, CG_TUPLE_F_IN, CG_TUPLE_F_RELATED, CG_TUPLE_F_SERVICE = 0, 1, 2, 4
+CG_CT_E_RX_CLOSING, CG_CT_E_TX_CLOSING, CG_CT_E_NAT46, CG_CT_E_LB_LOOPBACK, CG_CT_E_SEEN_NON_SYN = 1, 2, 4, 8, 16
+CG_CT_STATE_NONE, CG_CT_STATE_NEW, CG_CT_STATE_ESTABLISHED, CG_CT_STATE_REPLY, CG_CT_STATE_RELATED = 0, 1, 2, 3, 4
+CG_CT_OP_NONE, CG_CT_OP_CREATE, CG_CT_OP_DELETE = 0, 1, 2
+CG_DROP_CT_CREATE_FAILED = -155
 
 CG_PF_DYN4, CG_PF_DYN6, CG_PF_FIX4, CG_PF_FIX6 = 1, 2, 4, 8
 CG_XDP_DROP, CG_XDP_PASS = 1, 2
@@ -245,6 +252,21 @@ SIGNATURES = {
     "cg_l4_frames_verdicts_dev": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _u32, _p, _u32, _p, _p, _p, _p]),
     "cg_l4_frames_verdicts_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _u32, _p, _u32, _p, _p, _p]),
     "cg_diag_l4_frames_eval_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _u32, _p, _u32, _p, _p, _p, _p]),
+    "cg_ct_map_create": (C.c_int, [_u64, _u32, _u32, C.POINTER(_u32)]),
+    "cg_ct_map_destroy": (C.c_int, [_u64, _u32]),
+    "cg_ct_map_update": (C.c_int, [_u64, _u32, _p, _p, _sz]),
+    "cg_ct_map_delete": (C.c_int, [_u64, _u32, _p, _sz]),
+    "cg_ct_map_lookup": (C.c_int, [_u64, _u32, _p, _p]),
+    "cg_ct_map_dump": (C.c_int, [_u64, _u32, _p, _p, _sz, C.POINTER(_sz)]),
+    "cg_ct_map_apply": (C.c_int, [_u64, _u32, _p, _sz, _p, _p, _p]),
+    "cg_l4_frames_ct_verdicts_dev": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _u32, _p, _u32, _p, _u32, _p, _p, _p,
+                                               _p]),
+    "cg_l4_frames_ct_verdicts_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _u32, _p, _u32, _p, _u32, _p, _p,
+                                                _p]),
+    "cg_diag_l4_frames_ct_eval_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _u32, _p, _u32, _p, _u32, _p, _p,
+                                                 _p, _p]),
+    "cg_diag_ct_hash": (C.c_int, [_p, _sz, _p]),
+    "cg_diag_ct_map_info": (C.c_int, [_u64, _u32, _p, _p]),
 }
 
 

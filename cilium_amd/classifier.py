@@ -9,6 +9,10 @@ Mirrors the reference's entry points for the classification path:
 * ``EndpointMap`` — pkg/maps/lxcmap (WriteEndpoint/DeleteEntry/DumpToMap), and
   ``PolicyArray.frame_verdicts``: the ingress policy program from raw frames
   (bpf/bpf_lxc.c:1030-1058)
+* ``ConntrackMap`` — pkg/maps/ctmap (the TCP and ANY conntrack maps, per
+  endpoint or global): ``frame_verdicts(..., conntrack=ct)`` runs ct_lookup4/6
+  (bpf/lib/conntrack.h) in front of the policy, ``apply`` carries out the
+  CREATE / DELETE ops it reports
 * ``PreFilter``  — pkg/datapath/prefilter (Insert/Delete/Dump with revisions)
   + batched XDP ``check_filters`` (bpf/bpf_xdp.c:88-184)
 * ``Classifier.update_http_policy`` / ``http_verdicts`` — Envoy
@@ -43,6 +47,18 @@ ENDPOINT_KEY_DTYPE = np.dtype([("family", "u1"), ("pad", "u1", (3,)), ("addr", "
 ENDPOINT_INFO_DTYPE = np.dtype([("lxc_id", "<u2"), ("pad", "<u2"), ("flags", "<u4")])
 # cg_l4_frame_info: what the header walk found (cilium_gpu.h)
 FRAME_INFO_DTYPE = np.dtype([("t", L4_TUPLE_DTYPE), ("lxc_id", "<u2"), ("family", "u1"), ("pad", "u1")])
+# cg_ct_key / cg_ct_entry / cg_ct_record: the conntrack maps' keys and values, and what the lookup found per frame
+CT_KEY_DTYPE = np.dtype([("daddr", "u1", (16,)), ("saddr", "u1", (16,)), ("dport", "<u2"), ("sport", "<u2"),
+                         ("nexthdr", "u1"), ("flags", "u1"), ("pad", "<u2"), ("scope", "<u2"), ("family", "u1"),
+                         ("kind", "u1")])
+CT_ENTRY_DTYPE = np.dtype([("rx_packets", "<u8"), ("rx_bytes", "<u8"), ("tx_packets", "<u8"), ("tx_bytes", "<u8"),
+                           ("lifetime", "<u4"), ("flags", "<u2"), ("rev_nat_index", "<u2"), ("slave", "<u2"),
+                           ("tx_flags_seen", "u1"), ("rx_flags_seen", "u1"), ("src_sec_id", "<u4"),
+                           ("last_tx_report", "<u4"), ("last_rx_report", "<u4")])
+CT_RECORD_DTYPE = np.dtype([("state", "u1"), ("op", "u1"), ("loopback", "u1"), ("pad0", "u1"),
+                            ("rev_nat_index", "<u2"), ("pad1", "<u2"), ("pad2", "<u4", (2,)), ("key", CT_KEY_DTYPE),
+                            ("pad3", "<u4")])
+assert CT_KEY_DTYPE.itemsize == 44 and CT_ENTRY_DTYPE.itemsize == 56 and CT_RECORD_DTYPE.itemsize == 64
 assert ENDPOINT_KEY_DTYPE.itemsize == 20 and ENDPOINT_INFO_DTYPE.itemsize == 8 and FRAME_INFO_DTYPE.itemsize == 16
 assert L4_TUPLE_DTYPE.itemsize == 12 and KAFKA_REQ_DTYPE.itemsize == 64 and CIDR_DTYPE.itemsize == 20
 
@@ -105,6 +121,11 @@ class Classifier:
     def endpoint_map(self, max_entries: int = 0) -> "EndpointMap":
         """cilium_lxc: a local endpoint's address → {lxc_id, flags}."""
         return EndpointMap(self, max_entries)
+
+    def conntrack_map(self, max_entries: int = 0, global_map: bool = False) -> "ConntrackMap":
+        """cilium_ct{4,6}_* / cilium_ct_any{4,6}_*: the conntrack maps of every
+        scope (global_map: one global pair, every frame looks up scope 0)."""
+        return ConntrackMap(self, max_entries, global_map)
 
     # ------------------------------------------------------------ LPM --
     def prefilter(self, dyn4: bool = False, dyn6: bool = False, fix4: bool = True, fix6: bool = True,
@@ -790,18 +811,27 @@ class PolicyArray:
 
     def frame_verdicts(self, raw, off, *, lxc_ids=None, endpoints: Optional["EndpointMap"] = None, src_labels=None,
                        ipcache: Optional["IPCache"] = None, pkt_len=None, ignore_drop: bool = False,
-                       info: bool = False):
+                       info: bool = False, conntrack: Optional["ConntrackMap"] = None):
         """The ingress policy program's verdict per raw Ethernet frame, frame i
         = raw[off[i]:off[i+1]], parsed and judged on the device in one launch
         (cg_l4_frames_verdicts_host).  Exactly one of lxc_ids / endpoints (an
         EndpointMap looked up by destination address) and one of src_labels /
         ipcache (resolving the source address).  pkt_len: skb->len for the
         byte counters (default: the frame's length).  info=True also returns
-        the FRAME_INFO_DTYPE records."""
+        the FRAME_INFO_DTYPE records.  conntrack: the ConntrackMap that
+        ct_lookup4/6 read in front of the policy (cg_l4_frames_ct_verdicts_host);
+        info=True then returns (verdicts, FRAME_INFO records, CT_RECORD_DTYPE
+        records), the last being what ConntrackMap.apply takes."""
         raw, off, n, lxc, ep, lab, ipc, plen, mode = self._frame_args(raw, off, lxc_ids, endpoints, src_labels,
                                                                       ipcache, pkt_len, ignore_drop)
         out = np.zeros(max(n, 1), np.int32)
         fi = np.zeros(max(n, 1), FRAME_INFO_DTYPE) if info else None
+        if conntrack is not None:
+            rec = np.zeros(max(n, 1), CT_RECORD_DTYPE) if info else None
+            N.check(N.lib.cg_l4_frames_ct_verdicts_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep,
+                                                        _p(lab), ipc, _p(plen), conntrack.id, _p(out), _p(fi),
+                                                        _p(rec)))
+            return (out[:n], fi[:n], rec[:n]) if info else out[:n]
         N.check(N.lib.cg_l4_frames_verdicts_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep, _p(lab),
                                                  ipc, _p(plen), _p(out), _p(fi)))
         return (out[:n], fi[:n]) if info else out[:n]
@@ -809,10 +839,21 @@ class PolicyArray:
     def frame_verdicts_dev(self, d_raw, d_off, n: int, d_out, *, d_lxc_ids=None,
                            endpoints: Optional["EndpointMap"] = None, d_src_labels=None,
                            ipcache: Optional["IPCache"] = None, d_pkt_len=None, ignore_drop: bool = False,
-                           d_info=None, stream=None) -> None:
+                           d_info=None, stream=None, conntrack: Optional["ConntrackMap"] = None,
+                           d_records=None) -> None:
         """Device buffers (u8 blob, n + 1 u64 offsets, i32 verdicts, optional
-        16-byte info records), async on `stream`."""
+        16-byte info records; with conntrack optional 64-byte CT_RECORD_DTYPE
+        records), async on `stream`."""
         mode = N.CG_L4_INGRESS | (N.CG_L4_IGNORE_DROP if ignore_drop else 0)
+        if conntrack is not None:
+            N.check(N.lib.cg_l4_frames_ct_verdicts_dev(
+                self.cl.h, self.id, mode, _p(d_raw), _p(d_off), n, _p(d_lxc_ids),
+                endpoints.id if endpoints is not None else 0, _p(d_src_labels),
+                ipcache.id if ipcache is not None else 0, _p(d_pkt_len), conntrack.id, _p(d_out), _p(d_info),
+                _p(d_records), stream))
+            return
+        if d_records is not None:
+            raise ValueError("d_records needs a conntrack map")
         N.check(N.lib.cg_l4_frames_verdicts_dev(self.cl.h, self.id, mode, _p(d_raw), _p(d_off), n, _p(d_lxc_ids),
                                                 endpoints.id if endpoints is not None else 0, _p(d_src_labels),
                                                 ipcache.id if ipcache is not None else 0, _p(d_pkt_len), _p(d_out),
@@ -820,14 +861,24 @@ class PolicyArray:
 
     def frame_eval_host_diag(self, raw, off, *, lxc_ids=None, endpoints: Optional["EndpointMap"] = None,
                              src_labels=None, ipcache: Optional["IPCache"] = None, pkt_len=None,
-                             ignore_drop: bool = False, info: bool = False, l4_off: bool = False):
+                             ignore_drop: bool = False, info: bool = False, l4_off: bool = False,
+                             conntrack: Optional["ConntrackMap"] = None):
         """Diagnostics only: frame_verdicts by the kernel's own walk on the CPU
-        (no device, no counters).  l4_off=True appends the L4 offsets found."""
+        (no device, no counters).  l4_off=True appends the L4 offsets found.
+        With conntrack, info=True returns the CT_RECORD_DTYPE records after
+        the FRAME_INFO ones."""
         raw, off, n, lxc, ep, lab, ipc, plen, mode = self._frame_args(raw, off, lxc_ids, endpoints, src_labels,
                                                                       ipcache, pkt_len, ignore_drop)
         out = np.zeros(max(n, 1), np.int32)
         fi = np.zeros(max(n, 1), FRAME_INFO_DTYPE) if info else None
         lo = np.zeros(max(n, 1), np.uint32) if l4_off else None
+        if conntrack is not None:
+            rec = np.zeros(max(n, 1), CT_RECORD_DTYPE) if info else None
+            N.check(N.lib.cg_diag_l4_frames_ct_eval_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep,
+                                                         _p(lab), ipc, _p(plen), conntrack.id, _p(out), _p(fi),
+                                                         _p(rec), _p(lo)))
+            res = (out[:n],) + ((fi[:n], rec[:n]) if info else ()) + ((lo[:n],) if l4_off else ())
+            return res if len(res) > 1 else res[0]
         N.check(N.lib.cg_diag_l4_frames_eval_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep, _p(lab),
                                                   ipc, _p(plen), _p(out), _p(fi), _p(lo)))
         res = (out[:n],) + ((fi[:n],) if info else ()) + ((lo[:n],) if l4_off else ())
@@ -898,6 +949,113 @@ class EndpointMap:
 
     def destroy(self) -> None:
         N.check(N.lib.cg_endpoint_map_destroy(self.cl.h, self.id))
+
+
+class ConntrackMap:
+    """pkg/maps/ctmap on the device: the TCP and ANY conntrack maps of both
+    families and every scope in one object (cilium_gpu.h cg_ct_map_*).  A
+    scope is an endpoint's lxc id (its local maps); a global map holds scope
+    0 and every frame looks that up."""
+
+    def __init__(self, cl: Classifier, max_entries: int = 0, global_map: bool = False):
+        self.cl = cl
+        v = C.c_uint32()
+        N.check(N.lib.cg_ct_map_create(cl.h, max_entries, N.CG_CT_MAP_F_GLOBAL if global_map else 0, C.byref(v)))
+        self.id = v.value
+        self.max_entries = max_entries or 1 << 20
+        self.global_map = global_map
+
+    @staticmethod
+    def key(daddr, saddr, dport_be: int, sport_be: int, nexthdr: int, flags: int, *, kind: int = None,
+            scope: int = 0) -> np.ndarray:
+        """One CT_KEY_DTYPE key.  Addresses as strings or packed bytes; ports
+        as the datapath stores them (network order read as a u16); kind
+        defaults to the map get_ct_map4/6 picks for nexthdr."""
+        k = np.zeros(1, CT_KEY_DTYPE)
+        d, s_ = (a if isinstance(a, (bytes, bytearray)) else ipaddress.ip_address(a).packed for a in (daddr, saddr))
+        if len(d) != len(s_):
+            raise ValueError("daddr and saddr of one family")
+        k["daddr"][0, :len(d)] = np.frombuffer(bytes(d), np.uint8)
+        k["saddr"][0, :len(s_)] = np.frombuffer(bytes(s_), np.uint8)
+        k["family"] = 4 if len(d) == 4 else 6
+        k["dport"], k["sport"], k["nexthdr"], k["flags"], k["scope"] = dport_be, sport_be, nexthdr, flags, scope
+        k["kind"] = (N.CG_CT_MAP_TCP if nexthdr == 6 else N.CG_CT_MAP_ANY) if kind is None else kind
+        return k
+
+    @staticmethod
+    def _keys(keys) -> np.ndarray:
+        if isinstance(keys, np.ndarray):
+            if keys.dtype != CT_KEY_DTYPE:
+                raise ValueError("keys are CT_KEY_DTYPE")
+            return np.ascontiguousarray(keys).reshape(-1)
+        return np.concatenate(list(keys)) if len(keys) else np.zeros(0, CT_KEY_DTYPE)
+
+    def update(self, keys, values=None) -> None:
+        """map_update_elem for each key (values: CT_ENTRY_DTYPE, default all
+        zero); all or nothing (cg_ct_map_update)."""
+        k = self._keys(keys)
+        v = np.zeros(len(k), CT_ENTRY_DTYPE) if values is None else np.ascontiguousarray(values, CT_ENTRY_DTYPE)
+        if len(v) != len(k):
+            raise ValueError("one value per key")
+        N.check(N.lib.cg_ct_map_update(self.cl.h, self.id, _p(k) if len(k) else None, _p(v) if len(k) else None,
+                                       len(k)))
+
+    def delete(self, keys) -> None:
+        """CG_NOT_FOUND (nothing deleted) when a key is absent."""
+        k = self._keys(keys)
+        N.check(N.lib.cg_ct_map_delete(self.cl.h, self.id, _p(k) if len(k) else None, len(k)))
+
+    def lookup(self, key) -> Optional[np.ndarray]:
+        """The key's CT_ENTRY_DTYPE value, or None when it is absent."""
+        k = self._keys(key)[:1]
+        v = np.zeros(1, CT_ENTRY_DTYPE)
+        rc = N.lib.cg_ct_map_lookup(self.cl.h, self.id, _p(k), _p(v))
+        if rc == N.CG_NOT_FOUND:
+            return None
+        N.check(rc)
+        return v[0]
+
+    def dump(self) -> tuple[np.ndarray, np.ndarray]:
+        """(keys, values) in the order (scope, kind, family, the tuple's bytes as stored)."""
+        n = C.c_size_t()
+        N.check(N.lib.cg_ct_map_dump(self.cl.h, self.id, None, None, 0, C.byref(n)))
+        k = np.zeros(max(n.value, 1), CT_KEY_DTYPE)
+        v = np.zeros(max(n.value, 1), CT_ENTRY_DTYPE)
+        N.check(N.lib.cg_ct_map_dump(self.cl.h, self.id, _p(k), _p(v), n.value, C.byref(n)))
+        return k[:n.value], v[:n.value]
+
+    def apply(self, records: np.ndarray, pkt_len=None, src_labels=None) -> np.ndarray:
+        """Carry out the records' CREATE / DELETE ops in frame order
+        (cg_ct_map_apply): → per frame 0, or CG_DROP_CT_CREATE_FAILED where the
+        map was full."""
+        r = np.ascontiguousarray(records, CT_RECORD_DTYPE).reshape(-1)
+        n = len(r)
+        plen = None if pkt_len is None else np.ascontiguousarray(pkt_len, np.uint32).reshape(-1)
+        lab = None if src_labels is None else np.ascontiguousarray(src_labels, np.uint32).reshape(-1)
+        for a in (plen, lab):
+            if a is not None and len(a) != n:
+                raise ValueError("one pkt_len / src_label per record")
+        out = np.zeros(max(n, 1), np.int32)
+        N.check(N.lib.cg_ct_map_apply(self.cl.h, self.id, _p(r) if n else None, n, _p(plen) if n else None,
+                                      _p(lab) if n else None, _p(out)))
+        return out[:n]
+
+    def table_info(self) -> dict:
+        """Diagnostics: the built tables' buckets and recorded probe bound per family."""
+        b, p = np.zeros(2, np.uint32), np.zeros(2, np.uint32)
+        N.check(N.lib.cg_diag_ct_map_info(self.cl.h, self.id, _p(b), _p(p)))
+        return {4: (int(b[0]), int(p[0])), 6: (int(b[1]), int(p[1]))}
+
+    @staticmethod
+    def key_hashes(keys) -> np.ndarray:
+        """Diagnostics: the tables' hash of each key, before the bucket mask."""
+        k = ConntrackMap._keys(keys)
+        out = np.zeros(max(len(k), 1), np.uint32)
+        N.check(N.lib.cg_diag_ct_hash(_p(k) if len(k) else None, len(k), _p(out)))
+        return out[:len(k)]
+
+    def destroy(self) -> None:
+        N.check(N.lib.cg_ct_map_destroy(self.cl.h, self.id))
 
 
 def parse_cidr(s: str) -> np.ndarray:

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "ct_map.h"
 #include "endpoint_map.h"
 #include "engine.h"
 #include "frame_walk.h"
@@ -87,6 +88,12 @@ PolicyArrayState& get_arr(Engine& e, uint32_t id) {
 EndpointMapState& get_ep(Engine& e, uint32_t id) {
   auto it = e.epmaps.find(id);
   if (it == e.epmaps.end()) fail(CG_NOT_FOUND, "unknown endpoint map id");
+  return *it->second;
+}
+
+CtMapState& get_ct(Engine& e, uint32_t id) {
+  auto it = e.ctmaps.find(id);
+  if (it == e.ctmaps.end()) fail(CG_NOT_FOUND, "unknown conntrack map id");
   return *it->second;
 }
 
@@ -205,6 +212,7 @@ void cg_close(uint64_t h) {
     e->prefilters.clear();
     e->ipcaches.clear();
     e->epmaps.clear();
+    e->ctmaps.clear();
     e->selcaches.clear();
     e->http.reset();
     e->kafka.reset();
@@ -824,6 +832,147 @@ int cg_endpoint_map_dump(uint64_t h, uint32_t ep_id, cg_endpoint_key* keys, cg_e
   });
 }
 
+// -------------------------------------------------- conntrack maps ----
+// cilium_ct{4,6}_* / cilium_ct_any{4,6}_* with their values (ct_map.h).
+static CtMapState::Key make_ct_key(const cg_ct_key& k, bool global) {
+  if (k.family != 4 && k.family != 6) fail(CG_INVALID_ADDRESS, "conntrack key family must be 4 or 6");
+  if (k.kind != CG_CT_MAP_TCP && k.kind != CG_CT_MAP_ANY) fail(CG_INVALID_ARGUMENT, "conntrack key kind must be TCP or ANY");
+  if (k.flags & ~0x07u) fail(CG_INVALID_ARGUMENT, "conntrack key flags above TUPLE_F_SERVICE");
+  if (global && k.scope) fail(CG_INVALID_ARGUMENT, "a global conntrack map holds scope 0 only");
+  if (k.family == 4)
+    for (int i = 4; i < 16; ++i)
+      if (k.daddr[i] | k.saddr[i]) fail(CG_INVALID_ARGUMENT, "an IPv4 conntrack key uses address bytes 0..3");
+  return CtMapState::make_key(k);
+}
+
+int cg_ct_map_create(uint64_t h, uint32_t max_entries, uint32_t flags, uint32_t* ct_id) {
+  return guarded([&] {
+    auto e = get(h);
+    if (!ct_id) fail(CG_INVALID_ARGUMENT, "ct_id is NULL");
+    if (flags & ~CG_CT_MAP_F_GLOBAL) fail(CG_INVALID_ARGUMENT, "unknown conntrack map flags");
+    std::lock_guard<std::mutex> lk(e->mu);
+    auto p = std::make_unique<CtMapState>();
+    if (max_entries) p->max_entries = max_entries;
+    p->global = flags & CG_CT_MAP_F_GLOBAL;
+    const uint32_t id = e->next_id++;
+    e->ctmaps[id] = std::move(p);
+    *ct_id = id;
+  });
+}
+
+int cg_ct_map_destroy(uint64_t h, uint32_t ct_id) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    get_ct(*e, ct_id);
+    if (e->has_gpu()) dev_sync(*e, nullptr);
+    e->ctmaps.erase(ct_id);
+  });
+}
+
+int cg_ct_map_update(uint64_t h, uint32_t ct_id, const cg_ct_key* keys, const cg_ct_entry* values, size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    if (n && (!keys || !values)) fail(CG_INVALID_ARGUMENT, "NULL keys/values");
+    std::lock_guard<std::mutex> lk(e->mu);
+    CtMapState& p = get_ct(*e, ct_id);
+    std::map<CtMapState::Key, cg_ct_entry> batch;
+    for (size_t i = 0; i < n; ++i) batch[make_ct_key(keys[i], p.global)] = values[i];
+    size_t fresh = 0;
+    for (const auto& kv : batch) fresh += !p.entries.count(kv.first);
+    if (p.entries.size() + fresh > p.max_entries) fail(CG_MAP_FULL, "conntrack map full (max_entries)");
+    for (const auto& kv : batch) p.entries[kv.first] = kv.second;
+    p.dirty = true;
+  });
+}
+
+int cg_ct_map_delete(uint64_t h, uint32_t ct_id, const cg_ct_key* keys, size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    if (n && !keys) fail(CG_INVALID_ARGUMENT, "NULL keys");
+    std::lock_guard<std::mutex> lk(e->mu);
+    CtMapState& p = get_ct(*e, ct_id);
+    std::vector<CtMapState::Key> ks;
+    for (size_t i = 0; i < n; ++i) {
+      ks.push_back(make_ct_key(keys[i], p.global));
+      if (!p.entries.count(ks.back())) fail(CG_NOT_FOUND, "conntrack map: no entry for key");
+    }
+    for (const auto& k : ks) p.entries.erase(k);
+    p.dirty = true;
+  });
+}
+
+int cg_ct_map_lookup(uint64_t h, uint32_t ct_id, const cg_ct_key* key, cg_ct_entry* value) {
+  return guarded([&] {
+    auto e = get(h);
+    if (!key || !value) fail(CG_INVALID_ARGUMENT, "NULL key/value");
+    std::lock_guard<std::mutex> lk(e->mu);
+    CtMapState& p = get_ct(*e, ct_id);
+    auto it = p.entries.find(make_ct_key(*key, p.global));
+    if (it == p.entries.end()) fail(CG_NOT_FOUND, "conntrack map: no entry for key");
+    *value = it->second;
+  });
+}
+
+int cg_ct_map_dump(uint64_t h, uint32_t ct_id, cg_ct_key* keys, cg_ct_entry* values, size_t cap, size_t* n) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    CtMapState& p = get_ct(*e, ct_id);
+    size_t i = 0;
+    for (const auto& [k, v] : p.entries) {
+      if (i >= cap) break;
+      if (keys) keys[i] = CtMapState::key_of(k);
+      if (values) values[i] = v;
+      ++i;
+    }
+    if (n) *n = p.entries.size();
+  });
+}
+
+int cg_ct_map_apply(uint64_t h, uint32_t ct_id, const cg_ct_record* records, size_t n, const uint32_t* pkt_len,
+                    const uint32_t* src_labels, int32_t* results) {
+  return guarded([&] {
+    auto e = get(h);
+    if (n && !records) fail(CG_INVALID_ARGUMENT, "NULL records");
+    std::lock_guard<std::mutex> lk(e->mu);
+    CtMapState& p = get_ct(*e, ct_id);
+    // every record is checked before any is carried out
+    for (size_t i = 0; i < n; ++i) {
+      if (records[i].op > CG_CT_OP_DELETE) fail(CG_INVALID_ARGUMENT, "unknown conntrack op");
+      if (records[i].op != CG_CT_OP_NONE) make_ct_key(records[i].key, p.global);
+    }
+    for (size_t i = 0; i < n; ++i) {
+      const cg_ct_record& r = records[i];
+      if (results) results[i] = 0;
+      if (r.op == CG_CT_OP_NONE) continue;
+      const CtMapState::Key k = CtMapState::make_key(r.key);
+      if (r.op == CG_CT_OP_DELETE) {
+        p.dirty |= p.entries.erase(k) != 0;
+        continue;
+      }
+      cg_ct_key rel = r.key;  // the ICMP / ICMPv6 entry that relates errors to the flow
+      rel.nexthdr = r.key.family == 4 ? 1 : 58;
+      rel.sport = rel.dport = 0;
+      rel.flags = r.key.flags | CG_TUPLE_F_RELATED;
+      const CtMapState::Key kr = CtMapState::make_key(rel);
+      const size_t fresh = !p.entries.count(k) + (kr != k && !p.entries.count(kr));
+      if (p.entries.size() + fresh > p.max_entries) {
+        if (results) results[i] = CG_DROP_CT_CREATE_FAILED;
+        continue;
+      }
+      cg_ct_entry en{};
+      en.rx_packets = 1;
+      en.rx_bytes = pkt_len ? pkt_len[i] : 0;
+      en.src_sec_id = src_labels ? src_labels[i] : 0;
+      p.entries[k] = en;
+      en.flags |= CG_CT_E_SEEN_NON_SYN;
+      p.entries[kr] = en;
+      p.dirty = true;
+    }
+  });
+}
+
 // ------------------------------------------- L4 verdicts from frames ----
 // One snapshot of the policy array, the endpoint map and the ipcache, taken
 // under one hold of the handle lock; the launch holds all three.
@@ -832,6 +981,10 @@ struct FramesView {
   std::shared_ptr<DevTables> ep_keep, ipc_keep;
   EpMapDev ep{};
   IpcacheDev ipc{};
+  // the conntrack map of the cg_l4_frames_ct_* entries (has_ct), part of the same snapshot
+  bool has_ct = false;
+  std::shared_ptr<DevTables> ct_keep;
+  CtMapDev ct{};
 };
 static void check_frames_args(uint32_t mode, const void* lxc, uint32_t ep_id, const void* labels, uint32_t ipc_id) {
   if ((mode & ~CG_L4_IGNORE_DROP) != CG_L4_INGRESS)
@@ -840,9 +993,16 @@ static void check_frames_args(uint32_t mode, const void* lxc, uint32_t ep_id, co
   if ((labels != nullptr) == (ipc_id != 0))
     fail(CG_INVALID_ARGUMENT, "give src_labels or an ipcache, not both or neither");
 }
-static FramesView frames_view(Engine& e, uint32_t arr_id, uint32_t ep_id, uint32_t ipc_id) {
+static FramesView frames_view(Engine& e, uint32_t arr_id, uint32_t ep_id, uint32_t ipc_id, const uint32_t* ct_id) {
   std::lock_guard<std::mutex> lk(e.mu);
   FramesView v;
+  if (ct_id) {
+    CtMapState& p = get_ct(e, *ct_id);
+    if (p.dirty) p.rebuild(e);
+    v.has_ct = true;
+    v.ct_keep = p.tab;
+    v.ct = p.dev;
+  }
   v.arr = l4_array_view_locked(e, arr_id);
   if (ep_id) {
     EndpointMapState& p = get_ep(e, ep_id);
@@ -860,13 +1020,36 @@ static FramesView frames_view(Engine& e, uint32_t arr_id, uint32_t ep_id, uint32
 }
 static void frames_launch(Engine& e, const FramesView& v, uint32_t mode, const uint8_t* d_raw, const uint64_t* d_off,
                           size_t n, const uint16_t* d_lxc, const uint32_t* d_labels, const uint32_t* d_len,
-                          int32_t* d_out, void* d_info, void* st) {
-  check_launch(launch_l4_frames(v.arr.dev, v.ep_keep ? &v.ep : nullptr, v.ipc_keep ? &v.ipc : nullptr, d_raw, d_off, n,
-                                d_lxc, d_labels, d_len, d_out, d_info, mode, st, e.cus),
-               "l4 frames kernel launch");
+                          int32_t* d_out, void* d_info, void* d_recs, void* st) {
+  const EpMapDev* ep = v.ep_keep ? &v.ep : nullptr;
+  const IpcacheDev* ipc = v.ipc_keep ? &v.ipc : nullptr;
+  if (v.has_ct)
+    check_launch(launch_l4_frames_ct(v.arr.dev, ep, ipc, v.ct, d_raw, d_off, n, d_lxc, d_labels, d_len, d_out, d_info,
+                                     d_recs, mode, st, e.cus),
+                 "l4 frames conntrack kernel launch");
+  else
+    check_launch(launch_l4_frames(v.arr.dev, ep, ipc, d_raw, d_off, n, d_lxc, d_labels, d_len, d_out, d_info, mode, st,
+                                  e.cus),
+                 "l4 frames kernel launch");
+  fence(v.ct_keep, st);
   v.arr.keep->own.fence.record(st);
   fence(v.ep_keep, st);
   fence(v.ipc_keep, st);
+}
+
+// ct_id: NULL for the entries without conntrack, which launch l4_frames_kernel as before.
+static void frames_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw, const uint64_t* d_raw_off,
+                       size_t n, const uint16_t* d_lxc_ids, uint32_t ep_id, const uint32_t* d_src_labels,
+                       uint32_t ipc_id, const uint32_t* d_pkt_len, const uint32_t* ct_id, int32_t* d_verdicts,
+                       cg_l4_frame_info* d_info, cg_ct_record* d_recs, void* stream) {
+  auto e = get(h);
+  check_frames_args(mode, d_lxc_ids, ep_id, d_src_labels, ipc_id);
+  e->require_gpu();
+  if (!d_raw_off || (n && !d_verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
+  const FramesView v = frames_view(*e, arr_id, ep_id, ipc_id, ct_id);
+  e->set_device();
+  frames_launch(*e, v, mode, d_raw, d_raw_off, n, d_lxc_ids, d_src_labels, d_pkt_len, d_verdicts, d_info, d_recs,
+                stream_of(*e, stream));
 }
 
 int cg_l4_frames_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
@@ -874,52 +1057,79 @@ int cg_l4_frames_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const 
                               const uint32_t* d_src_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
                               int32_t* d_verdicts, cg_l4_frame_info* d_info, void* stream) {
   return guarded([&] {
-    auto e = get(h);
-    check_frames_args(mode, d_lxc_ids, ep_id, d_src_labels, ipc_id);
-    e->require_gpu();
-    if (!d_raw_off || (n && !d_verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
-    const FramesView v = frames_view(*e, arr_id, ep_id, ipc_id);
-    e->set_device();
-    frames_launch(*e, v, mode, d_raw, d_raw_off, n, d_lxc_ids, d_src_labels, d_pkt_len, d_verdicts, d_info,
-                  stream_of(*e, stream));
+    frames_dev(h, arr_id, mode, d_raw, d_raw_off, n, d_lxc_ids, ep_id, d_src_labels, ipc_id, d_pkt_len, nullptr,
+               d_verdicts, d_info, nullptr, stream);
+  });
+}
+
+int cg_l4_frames_ct_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
+                                 const uint64_t* d_raw_off, size_t n, const uint16_t* d_lxc_ids, uint32_t ep_id,
+                                 const uint32_t* d_src_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
+                                 uint32_t ct_id, int32_t* d_verdicts, cg_l4_frame_info* d_info,
+                                 cg_ct_record* d_records, void* stream) {
+  return guarded([&] {
+    frames_dev(h, arr_id, mode, d_raw, d_raw_off, n, d_lxc_ids, ep_id, d_src_labels, ipc_id, d_pkt_len, &ct_id,
+               d_verdicts, d_info, d_records, stream);
   });
 }
 
 static void* stage_in(StagingSlot& sl, int i, const void* src, size_t bytes);
+
+static void frames_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw, const uint64_t* raw_off,
+                        size_t n, const uint16_t* lxc_ids, uint32_t ep_id, const uint32_t* src_labels,
+                        uint32_t ipc_id, const uint32_t* pkt_len, const uint32_t* ct_id, int32_t* verdicts,
+                        cg_l4_frame_info* info, cg_ct_record* recs) {
+  auto e = get(h);
+  check_frames_args(mode, lxc_ids, ep_id, src_labels, ipc_id);
+  e->require_gpu();
+  if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
+  const uint64_t lo = raw_off[0], bytes = raw_off[n] > lo ? raw_off[n] - lo : 0;
+  if (bytes && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
+  const FramesView v = frames_view(*e, arr_id, ep_id, ipc_id, ct_id);
+  if (!n) return;
+  e->set_device();
+  auto lease = e->staging.acquire(e->device);
+  const auto st = (hipStream_t)lease->stream;
+  // the blob's window [raw_off[0], raw_off[n]) is what travels; the kernel adds the offsets to d_raw
+  const uint8_t* d_win = (const uint8_t*)stage_in(*lease, 0, raw + lo, bytes);
+  const uint8_t* d_raw = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(d_win) - lo);
+  const uint64_t* d_off = (const uint64_t*)stage_in(*lease, 1, raw_off, (n + 1) * 8);
+  const uint16_t* d_lxc = lxc_ids ? (const uint16_t*)stage_in(*lease, 2, lxc_ids, n * 2) : nullptr;
+  const uint32_t* d_lab = src_labels ? (const uint32_t*)stage_in(*lease, 3, src_labels, n * 4) : nullptr;
+  const uint32_t* d_len = pkt_len ? (const uint32_t*)stage_in(*lease, 4, pkt_len, n * 4) : nullptr;
+  int32_t* d_out = (int32_t*)lease->dev_buf(5, n * 4);
+  void* d_info = info ? lease->dev_buf(6, n * sizeof(cg_l4_frame_info)) : nullptr;
+  void* d_recs = recs ? lease->dev_buf(7, n * sizeof(cg_ct_record)) : nullptr;
+  frames_launch(*e, v, mode, d_raw, d_off, n, d_lxc, d_lab, d_len, d_out, d_info, d_recs, st);
+  int32_t* h_out = (int32_t*)lease->host_buf(5, n * 4);
+  hip_check(hipMemcpyAsync(h_out, d_out, n * 4, hipMemcpyDeviceToHost, st), "D2H");
+  void* h_info = info ? lease->host_buf(6, n * sizeof(cg_l4_frame_info)) : nullptr;
+  if (info) hip_check(hipMemcpyAsync(h_info, d_info, n * sizeof(cg_l4_frame_info), hipMemcpyDeviceToHost, st), "D2H");
+  void* h_recs = recs ? lease->host_buf(7, n * sizeof(cg_ct_record)) : nullptr;
+  if (recs) hip_check(hipMemcpyAsync(h_recs, d_recs, n * sizeof(cg_ct_record), hipMemcpyDeviceToHost, st), "D2H");
+  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  memcpy(verdicts, h_out, n * 4);
+  if (info) memcpy(info, h_info, n * sizeof(cg_l4_frame_info));
+  if (recs) memcpy(recs, h_recs, n * sizeof(cg_ct_record));
+}
 
 int cg_l4_frames_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
                                const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
                                const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
                                int32_t* verdicts, cg_l4_frame_info* info) {
   return guarded([&] {
-    auto e = get(h);
-    check_frames_args(mode, lxc_ids, ep_id, src_labels, ipc_id);
-    e->require_gpu();
-    if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
-    const uint64_t lo = raw_off[0], bytes = raw_off[n] > lo ? raw_off[n] - lo : 0;
-    if (bytes && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
-    const FramesView v = frames_view(*e, arr_id, ep_id, ipc_id);
-    if (!n) return;
-    e->set_device();
-    auto lease = e->staging.acquire(e->device);
-    const auto st = (hipStream_t)lease->stream;
-    // the blob's window [raw_off[0], raw_off[n]) is what travels; the kernel adds the offsets to d_raw
-    const uint8_t* d_win = (const uint8_t*)stage_in(*lease, 0, raw + lo, bytes);
-    const uint8_t* d_raw = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(d_win) - lo);
-    const uint64_t* d_off = (const uint64_t*)stage_in(*lease, 1, raw_off, (n + 1) * 8);
-    const uint16_t* d_lxc = lxc_ids ? (const uint16_t*)stage_in(*lease, 2, lxc_ids, n * 2) : nullptr;
-    const uint32_t* d_lab = src_labels ? (const uint32_t*)stage_in(*lease, 3, src_labels, n * 4) : nullptr;
-    const uint32_t* d_len = pkt_len ? (const uint32_t*)stage_in(*lease, 4, pkt_len, n * 4) : nullptr;
-    int32_t* d_out = (int32_t*)lease->dev_buf(5, n * 4);
-    void* d_info = info ? lease->dev_buf(6, n * sizeof(cg_l4_frame_info)) : nullptr;
-    frames_launch(*e, v, mode, d_raw, d_off, n, d_lxc, d_lab, d_len, d_out, d_info, st);
-    int32_t* h_out = (int32_t*)lease->host_buf(5, n * 4);
-    hip_check(hipMemcpyAsync(h_out, d_out, n * 4, hipMemcpyDeviceToHost, st), "D2H");
-    void* h_info = info ? lease->host_buf(6, n * sizeof(cg_l4_frame_info)) : nullptr;
-    if (info) hip_check(hipMemcpyAsync(h_info, d_info, n * sizeof(cg_l4_frame_info), hipMemcpyDeviceToHost, st), "D2H");
-    hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-    memcpy(verdicts, h_out, n * 4);
-    if (info) memcpy(info, h_info, n * sizeof(cg_l4_frame_info));
+    frames_host(h, arr_id, mode, raw, raw_off, n, lxc_ids, ep_id, src_labels, ipc_id, pkt_len, nullptr, verdicts, info,
+                nullptr);
+  });
+}
+
+int cg_l4_frames_ct_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                  const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
+                                  const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                  uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info, cg_ct_record* records) {
+  return guarded([&] {
+    frames_host(h, arr_id, mode, raw, raw_off, n, lxc_ids, ep_id, src_labels, ipc_id, pkt_len, &ct_id, verdicts, info,
+                records);
   });
 }
 
@@ -2734,72 +2944,136 @@ int cg_diag_l4_array_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const
 // the array, the endpoint map and the ipcache.  No device, no counters.
 // l4_off (may be NULL): the L4 offset the walk found, 0 where it did not get
 // that far.
+// ct_id: NULL without conntrack (frame_verdict), else frame_ct_verdict over
+// that map's host tables and a record per frame.
+static void frames_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw, const uint64_t* raw_off,
+                             size_t n, const uint16_t* lxc_ids, uint32_t ep_id, const uint32_t* src_labels,
+                             uint32_t ipc_id, const uint32_t* pkt_len, const uint32_t* ct_id, int32_t* verdicts,
+                             cg_l4_frame_info* info, cg_ct_record* ct_recs, uint32_t* l4_off) {
+  auto e = get(h);
+  check_frames_args(mode, lxc_ids, ep_id, src_labels, ipc_id);
+  if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
+  const uint64_t wlo = raw_off[0], whi = raw_off[n];
+  if (whi > wlo && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
+  std::lock_guard<std::mutex> lk(e->mu);
+  PolicyArrayState& a = get_arr(*e, arr_id);
+  // the array as the kernel sees it: slot words over the members' host views
+  std::map<uint32_t, uint32_t> word;
+  std::vector<L4Dev> recs;
+  for (const auto& ref : a.refs) {
+    PolicyMapState& m = get_map(*e, ref.first);
+    if (m.dirty) m.rebuild(*e);
+    word.emplace(ref.first, (uint32_t)recs.size() + 1);
+    recs.push_back(m.host_view());
+  }
+  std::vector<uint32_t> slot(CG_POLICY_ARRAY_SLOTS, 0u);
+  for (uint32_t s = 0; s < CG_POLICY_ARRAY_SLOTS; ++s)
+    if (a.slot_map[s]) slot[s] = word[a.slot_map[s]];
+  if (recs.empty()) recs.push_back(L4Dev{});
+  const L4ArrDev A{slot.data(), recs.data()};
+  EpMapDev E{};
+  IpcacheDev ipc{};
+  if (ep_id) {
+    EndpointMapState& p = get_ep(*e, ep_id);
+    if (p.dirty) p.rebuild(*e);
+    E = p.host_view();
+  }
+  if (ipc_id) {
+    IpcacheState& p = get_ipc(*e, ipc_id);
+    if (p.dirty) p.rebuild(*e);
+    ipc = p.host_view();
+  }
+  CtMapDev C{};
+  if (ct_id) {
+    CtMapState& p = get_ct(*e, *ct_id);
+    if (p.dirty) p.rebuild(*e);
+    C = p.host_view();
+  }
+  const uint8_t* lo = raw + wlo;
+  const uint8_t* hi = whi > wlo ? raw + whi : lo;
+  for (size_t i = 0; i < n; ++i) {
+    uint64_t start;
+    const uint32_t len = frame_range(raw_off[i], raw_off[i + 1], wlo, whi, &start);
+    const uint8_t* base = raw + start;
+    auto ld = [&](uint32_t o) {
+      uint32_t v = 0;
+      for (int k = 0; k < 4; ++k) {
+        const uint8_t* p = base + o + k;
+        if (p >= lo && p < hi) v |= (uint32_t)*p << (8 * k);
+      }
+      return v;
+    };
+    auto count = [](const L4Dev&, uint32_t) {};
+    const uint32_t plen = pkt_len ? pkt_len[i] : len;
+    const uint32_t lxc = lxc_ids ? lxc_ids[i] : 0u, label = src_labels ? src_labels[i] : 0u;
+    cg_l4_frame_info fi;
+    uint32_t lo4 = 0;
+    int32_t v;
+    if (ct_id) {
+      CtRecWords r;
+      if (ep_id && ipc_id)
+        v = frame_ct_verdict<true, true>(A, E, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
+      else if (ep_id)
+        v = frame_ct_verdict<true, false>(A, E, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
+      else if (ipc_id)
+        v = frame_ct_verdict<false, true>(A, E, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
+      else
+        v = frame_ct_verdict<false, false>(A, E, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
+      if (ct_recs) memcpy(&ct_recs[i], r.w, sizeof(cg_ct_record));
+    } else if (ep_id && ipc_id)
+      v = frame_verdict<true, true>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
+    else if (ep_id) v = frame_verdict<true, false>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
+    else if (ipc_id) v = frame_verdict<false, true>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
+    else v = frame_verdict<false, false>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
+    verdicts[i] = v;
+    if (info) info[i] = fi;
+    if (l4_off) l4_off[i] = lo4;
+  }
+}
+
 int cg_diag_l4_frames_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
                                 const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
                                 const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
                                 int32_t* verdicts, cg_l4_frame_info* info, uint32_t* l4_off) {
   return guarded([&] {
-    auto e = get(h);
-    check_frames_args(mode, lxc_ids, ep_id, src_labels, ipc_id);
-    if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
-    const uint64_t wlo = raw_off[0], whi = raw_off[n];
-    if (whi > wlo && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
-    std::lock_guard<std::mutex> lk(e->mu);
-    PolicyArrayState& a = get_arr(*e, arr_id);
-    // the array as the kernel sees it: slot words over the members' host views
-    std::map<uint32_t, uint32_t> word;
-    std::vector<L4Dev> recs;
-    for (const auto& ref : a.refs) {
-      PolicyMapState& m = get_map(*e, ref.first);
-      if (m.dirty) m.rebuild(*e);
-      word.emplace(ref.first, (uint32_t)recs.size() + 1);
-      recs.push_back(m.host_view());
-    }
-    std::vector<uint32_t> slot(CG_POLICY_ARRAY_SLOTS, 0u);
-    for (uint32_t s = 0; s < CG_POLICY_ARRAY_SLOTS; ++s)
-      if (a.slot_map[s]) slot[s] = word[a.slot_map[s]];
-    if (recs.empty()) recs.push_back(L4Dev{});
-    const L4ArrDev A{slot.data(), recs.data()};
-    EpMapDev E{};
-    IpcacheDev ipc{};
-    if (ep_id) {
-      EndpointMapState& p = get_ep(*e, ep_id);
-      if (p.dirty) p.rebuild(*e);
-      E = p.host_view();
-    }
-    if (ipc_id) {
-      IpcacheState& p = get_ipc(*e, ipc_id);
-      if (p.dirty) p.rebuild(*e);
-      ipc = p.host_view();
-    }
-    const uint8_t* lo = raw + wlo;
-    const uint8_t* hi = whi > wlo ? raw + whi : lo;
+    frames_eval_host(h, arr_id, mode, raw, raw_off, n, lxc_ids, ep_id, src_labels, ipc_id, pkt_len, nullptr, verdicts,
+                     info, nullptr, l4_off);
+  });
+}
+
+int cg_diag_l4_frames_ct_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                   const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
+                                   const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                   uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
+                                   cg_ct_record* records, uint32_t* l4_off) {
+  return guarded([&] {
+    frames_eval_host(h, arr_id, mode, raw, raw_off, n, lxc_ids, ep_id, src_labels, ipc_id, pkt_len, &ct_id, verdicts,
+                     info, records, l4_off);
+  });
+}
+
+int cg_diag_ct_hash(const cg_ct_key* keys, size_t n, uint32_t* hashes) {
+  return guarded([&] {
+    if (n && (!keys || !hashes)) fail(CG_INVALID_ARGUMENT, "NULL keys/hashes");
     for (size_t i = 0; i < n; ++i) {
-      uint64_t start;
-      const uint32_t len = frame_range(raw_off[i], raw_off[i + 1], wlo, whi, &start);
-      const uint8_t* base = raw + start;
-      auto ld = [&](uint32_t o) {
-        uint32_t v = 0;
-        for (int k = 0; k < 4; ++k) {
-          const uint8_t* p = base + o + k;
-          if (p >= lo && p < hi) v |= (uint32_t)*p << (8 * k);
-        }
-        return v;
-      };
-      auto count = [](const L4Dev&, uint32_t) {};
-      const uint32_t plen = pkt_len ? pkt_len[i] : len;
-      const uint32_t lxc = lxc_ids ? lxc_ids[i] : 0u, label = src_labels ? src_labels[i] : 0u;
-      cg_l4_frame_info fi;
-      uint32_t lo4 = 0;
-      int32_t v;
-      if (ep_id && ipc_id) v = frame_verdict<true, true>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
-      else if (ep_id) v = frame_verdict<true, false>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
-      else if (ipc_id) v = frame_verdict<false, true>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
-      else v = frame_verdict<false, false>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
-      verdicts[i] = v;
-      if (info) info[i] = fi;
-      if (l4_off) l4_off[i] = lo4;
+      const CtMapState::Key k = make_ct_key(keys[i], false);
+      hashes[i] = keys[i].family == 4 ? ct_hash(CtMapState::dev_key<kCt4Words>(k))
+                                      : ct_hash(CtMapState::dev_key<kCt6Words>(k));
     }
+  });
+}
+
+int cg_diag_ct_map_info(uint64_t h, uint32_t ct_id, uint32_t buckets[2], uint32_t probes[2]) {
+  return guarded([&] {
+    auto e = get(h);
+    if (!buckets || !probes) fail(CG_INVALID_ARGUMENT, "NULL buckets/probes");
+    std::lock_guard<std::mutex> lk(e->mu);
+    CtMapState& p = get_ct(*e, ct_id);
+    if (p.dirty) p.rebuild(*e);
+    buckets[0] = p.mask4 + 1;
+    buckets[1] = p.mask6 + 1;
+    probes[0] = p.probes4;
+    probes[1] = p.probes6;
   });
 }
 

@@ -160,6 +160,7 @@ struct PolicyArrayState;
 struct PrefilterState;
 struct IpcacheState;
 struct EndpointMapState;
+struct CtMapState;
 struct SelcacheState;
 struct HttpSnapshot;
 struct KafkaSnapshot;
@@ -178,6 +179,7 @@ struct Engine {
   std::map<uint32_t, std::unique_ptr<PrefilterState>> prefilters;
   std::map<uint32_t, std::unique_ptr<IpcacheState>> ipcaches;
   std::map<uint32_t, std::unique_ptr<EndpointMapState>> epmaps;  // cilium_lxc (endpoint_map.h)
+  std::map<uint32_t, std::unique_ptr<CtMapState>> ctmaps;        // the conntrack maps (ct_map.h)
   std::map<uint32_t, std::unique_ptr<SelcacheState>> selcaches;
   std::shared_ptr<HttpSnapshot> http;
   std::shared_ptr<KafkaSnapshot> kafka;

@@ -8,7 +8,9 @@
 // conntrack table: every packet is CT_NEW, so the tuple that reaches the
 // policy is the reversed one (lib/conntrack.h:579-584, :422-426); tc_index and
 // cb[CB_POLICY] are 0.  skb_load_bytes(off, n) fails when off + n passes the
-// frame's length, and revalidate_data uses the same bound.
+// frame's length, and revalidate_data uses the same bound.  ct_walk.h puts the
+// lookup against a conntrack map behind frame_verdict for the callers who
+// pass one.
 //
 // ld(off): the four bytes at frame offset off, the first in bits 0..7.  The
 // walk asks only for offsets it has checked against the length; bytes of the

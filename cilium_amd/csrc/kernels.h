@@ -4,6 +4,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "ct_walk.h"
 #include "dev_types.h"
 
 namespace cg {
@@ -30,6 +31,12 @@ int launch_l4_array(const L4ArrDev& A, const IpcacheDev& ipc, int family, const 
 int launch_l4_frames(const L4ArrDev& A, const EpMapDev* E, const IpcacheDev* ipc, const uint8_t* raw,
                      const uint64_t* off, size_t n, const uint16_t* lxc, const uint32_t* labels,
                      const uint32_t* pkt_len, int32_t* out, void* info, uint32_t mode, void* stream, int cus);
+// The same with the conntrack lookup (ct_walk.h) over C; recs (64-byte
+// cg_ct_record per frame) may be NULL.
+int launch_l4_frames_ct(const L4ArrDev& A, const EpMapDev* E, const IpcacheDev* ipc, const CtMapDev& C,
+                        const uint8_t* raw, const uint64_t* off, size_t n, const uint16_t* lxc, const uint32_t* labels,
+                        const uint32_t* pkt_len, int32_t* out, void* info, void* recs, uint32_t mode, void* stream,
+                        int cus);
 int launch_lpm(const LpmDev& t, bool v4_filter, bool v6_filter, const uint32_t* v4, size_t n4,
                uint8_t* out4, const uint8_t* v6, size_t n6, uint8_t* out6, void* stream, int cus);
 // order (optional): out[order[slot]] instead of out[slot] (request order;

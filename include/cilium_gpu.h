@@ -334,6 +334,167 @@ int cg_l4_frames_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const
                                const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
                                int32_t* verdicts, cg_l4_frame_info* info /* may be NULL */);
 
+/* The conntrack maps, cilium_ct{4,6}_* and cilium_ct_any{4,6}_* (pkg/maps/ctmap,
+ * bpf/lib/conntrack.h): one object holds the TCP and the ANY map of both
+ * families, for every scope.  A key is struct ipv4_ct_tuple / ipv6_ct_tuple
+ * exactly as the datapath stores it (bpf/lib/common.h:338-378,
+ * ctmap/ipv4.go:29-36: ports in network order, flags TUPLE_F_*) together with
+ *  - kind: which map.  get_ct_map4/6 (bpf_lxc.c:101-107) picks the TCP map for
+ *    nexthdr == TCP and the ANY map otherwise, and ct_create* writes a flow's
+ *    ICMP "related" key into the flow's own map (conntrack.h:756-769,
+ *    :645-664): a TCP flow's related key lives in the TCP map, where an ICMP
+ *    error, looked up in the ANY map, does not find it;
+ *  - scope: conntrack maps are per endpoint (cilium_ct4_<id>: scope = the lxc
+ *    id) or global.  A map created with CG_CT_MAP_F_GLOBAL holds scope 0 only,
+ *    and every frame looks up scope 0.
+ * On the device it is an exact-match table of 128-byte buckets sized for HBM
+ * (DESIGN.md 2), published by swap like every other table: a verdict call
+ * sees one snapshot of the whole map, taken under the handle lock together
+ * with the array's, the endpoint map's and the ipcache's, so a concurrent
+ * cg_ct_map_* update is seen by that call entirely or not at all.  The device
+ * holds rev_nat_index and lb_loopback per key; the rest of the entry stays on
+ * the host for lookup and dump. */
+#define CG_CT_MAP_TCP 0u
+#define CG_CT_MAP_ANY 1u
+#define CG_CT_MAP_F_GLOBAL 1u
+#define CG_TUPLE_F_OUT 0u /* bpf/lib/conntrack.h:63-66 */
+#define CG_TUPLE_F_IN 1u
+#define CG_TUPLE_F_RELATED 2u
+#define CG_TUPLE_F_SERVICE 4u
+typedef struct {
+  uint8_t daddr[16]; /* network byte order; v4 uses [0..3], the rest 0 */
+  uint8_t saddr[16];
+  uint16_t dport;    /* network byte order, as stored */
+  uint16_t sport;
+  uint8_t nexthdr;
+  uint8_t flags;     /* CG_TUPLE_F_*: bits above 0x07 are CG_INVALID_ARGUMENT */
+  uint16_t pad;
+  uint16_t scope;
+  uint8_t family;    /* 4 or 6 */
+  uint8_t kind;      /* CG_CT_MAP_TCP / CG_CT_MAP_ANY */
+} cg_ct_key;         /* 44 bytes */
+/* struct ct_entry (bpf/lib/common.h:380-406), field for field; `flags` is its
+ * bit field as one u16. */
+#define CG_CT_E_RX_CLOSING 0x01u
+#define CG_CT_E_TX_CLOSING 0x02u
+#define CG_CT_E_NAT46 0x04u
+#define CG_CT_E_LB_LOOPBACK 0x08u
+#define CG_CT_E_SEEN_NON_SYN 0x10u
+typedef struct {
+  uint64_t rx_packets, rx_bytes, tx_packets, tx_bytes;
+  uint32_t lifetime;
+  uint16_t flags; /* CG_CT_E_* */
+  uint16_t rev_nat_index;
+  uint16_t slave;
+  uint8_t tx_flags_seen, rx_flags_seen;
+  uint32_t src_sec_id;
+  uint32_t last_tx_report, last_rx_report;
+} cg_ct_entry; /* 56 bytes */
+/* max_entries bounds the object's keys, all kinds, families and scopes
+ * together; 0 = 1 << 20. */
+int cg_ct_map_create(uint64_t h, uint32_t max_entries, uint32_t flags, uint32_t* ct_id);
+int cg_ct_map_destroy(uint64_t h, uint32_t ct_id);
+/* map_update_elem(BPF_ANY) for each pair; a key given twice keeps its last
+ * value.  All-or-nothing as cg_endpoint_map_update: CG_INVALID_ADDRESS for a
+ * family other than 4 / 6, CG_INVALID_ARGUMENT for an unknown kind, flag bits
+ * above 0x07, a v4 key with address bytes past the fourth, or a non-zero
+ * scope on a global map; CG_MAP_FULL when the batch would exceed max_entries;
+ * and nothing is applied. */
+int cg_ct_map_update(uint64_t h, uint32_t ct_id, const cg_ct_key* keys, const cg_ct_entry* values, size_t n);
+/* CG_NOT_FOUND (nothing deleted) if any key is absent. */
+int cg_ct_map_delete(uint64_t h, uint32_t ct_id, const cg_ct_key* keys, size_t n);
+int cg_ct_map_lookup(uint64_t h, uint32_t ct_id, const cg_ct_key* key, cg_ct_entry* value);
+/* Keys in the order (scope, kind, family, then the tuple's bytes as the
+ * datapath stores them: daddr, saddr, dport, sport, nexthdr, flags, compared
+ * byte by byte); *n gets the total. */
+int cg_ct_map_dump(uint64_t h, uint32_t ct_id, cg_ct_key* keys, cg_ct_entry* values, size_t cap, size_t* n);
+
+/* cg_l4_frames_verdicts_* with the conntrack lookup in its place:
+ * ct_lookup4 / ct_lookup6 (bpf/lib/conntrack.h:467-590, :310-437) in front of
+ * the policy, and the tail of ipv4_policy / ipv6_policy that acts on its
+ * result (bpf_lxc.c:948-976, :814-840).  Everything cg_l4_frames_verdicts_*
+ * state holds, and a frame whose walk returns before the lookup (every code
+ * of the two orders above, the walk's DROP_* codes included) gets that code
+ * and an all-zero record.  For the others:
+ *  - the tuple is the header's saddr / daddr as found (IPv6: before the
+ *    rev-NAT bits of the destination are zeroed, bpf_lxc.c:764-766),
+ *    TUPLE_F_OUT, nexthdr, and the ports of the head of ct_lookup*: the four
+ *    port bytes in {dport, sport}; ICMP dest-unreach / time-exceeded /
+ *    parameter-problem (3, 11, 12) and ICMPv6 dest-unreach / packet-too-big /
+ *    time-exceeded / parameter-problem (1..4) set TUPLE_F_RELATED, an echo
+ *    reply sets dport = 8 / 128, an echo request sport = 8 / 128 (raw u16);
+ *  - the map is the TCP one for nexthdr 6, else the ANY one; the scope is the
+ *    frame's lxc id, or 0 on a global map;
+ *  - the tuple as loaded is looked up first: a hit is CT_RELATED with
+ *    TUPLE_F_RELATED, else CT_REPLY.  On a miss the tuple is reversed
+ *    (addresses and ports swapped, TUPLE_F_IN flipped) and looked up again:
+ *    CT_ESTABLISHED, or CT_NEW.  __ct_lookup never tests an entry's lifetime
+ *    or closing bits for its result, so neither does this;
+ *  - the policy is evaluated exactly as cg_l4_frames_verdicts_* evaluate it,
+ *    whatever the state, and its counters move (the reference's call on a
+ *    REPLY / RELATED packet passes the unreversed dport; here the key and its
+ *    counters are those of the call without conntrack);
+ *  - REPLY / RELATED: verdict 0, never a proxy port.  Policy denies
+ *    otherwise: CG_DROP_POLICY, and op DELETE of the matched key if the state
+ *    was ESTABLISHED.  NEW and allowed: op CREATE, the policy's verdict (0 or
+ *    the proxy port).  ESTABLISHED and allowed: the policy's verdict, no op.
+ *    CG_L4_IGNORE_DROP turns the policy's denial into 0 before this, as the
+ *    datapath built with IGNORE_DROP does.
+ * The map is read, never written: the ops are reported in the records and
+ * cg_ct_map_apply carries them out.  Within one call a second packet of a
+ * flow that the first would have created still reads CT_NEW; both get CREATE,
+ * which apply makes idempotent.  Not modelled: lifetime and flags-seen
+ * updates, CONNTRACK_ACCOUNTING, rev-NAT (rev_nat_index / loopback are
+ * reported, not acted on), NAT46. */
+#define CG_CT_STATE_NONE 0u /* the walk did not reach the lookup */
+#define CG_CT_STATE_NEW 1u  /* 1 + CT_NEW .. CT_RELATED (bpf/lib/common.h:331-336) */
+#define CG_CT_STATE_ESTABLISHED 2u
+#define CG_CT_STATE_REPLY 3u
+#define CG_CT_STATE_RELATED 4u
+#define CG_CT_OP_NONE 0u
+#define CG_CT_OP_CREATE 1u
+#define CG_CT_OP_DELETE 2u
+#define CG_DROP_CT_CREATE_FAILED (-155) /* bpf/lib/common.h:262 */
+/* 64 bytes per frame.  key: the tuple the op applies to, in the form the
+ * reference writes or deletes it — after the reversal (what ct_create*
+ * receives, what matched as ESTABLISHED); for REPLY / RELATED the tuple as it
+ * matched.  key.kind, key.family and key.scope name the map looked up.
+ * rev_nat_index / loopback: the matched entry's, 0 for NEW. */
+typedef struct {
+  uint8_t state; /* CG_CT_STATE_* */
+  uint8_t op;    /* CG_CT_OP_* */
+  uint8_t loopback;
+  uint8_t pad0;
+  uint16_t rev_nat_index;
+  uint16_t pad1;
+  uint32_t pad2[2];
+  cg_ct_key key;
+  uint32_t pad3;
+} cg_ct_record;
+/* ct_id: the conntrack map; d_records / records may be NULL. */
+int cg_l4_frames_ct_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
+                                 const uint64_t* d_raw_off, size_t n, const uint16_t* d_lxc_ids, uint32_t ep_id,
+                                 const uint32_t* d_src_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
+                                 uint32_t ct_id, int32_t* d_verdicts, cg_l4_frame_info* d_info,
+                                 cg_ct_record* d_records, void* stream);
+int cg_l4_frames_ct_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                  const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
+                                  const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                  uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info, cg_ct_record* records);
+/* Carry out the records' ops on the map, in frame order (host side):
+ *  - CREATE: ct_create4/6 with a zero ct_state (conntrack.h:691-772, :616-667):
+ *    the flow's key, then the ICMP / ICMPv6 related key (same addresses, ports
+ *    0, flags | TUPLE_F_RELATED, same kind and scope), each with rx_packets =
+ *    1, rx_bytes = pkt_len[i] (NULL: 0), src_sec_id = src_labels[i] (NULL: 0);
+ *    the related entry has seen_non_syn set.  Existing keys are overwritten,
+ *    so a duplicate CREATE leaves one pair;
+ *  - DELETE: the key is removed; a key already gone is not an error
+ *    (ct_delete* ignores it).
+ * results[i] (may be NULL): 0, or CG_DROP_CT_CREATE_FAILED when the frame's
+ * new keys did not fit under max_entries; neither key is written then. */
+int cg_ct_map_apply(uint64_t h, uint32_t ct_id, const cg_ct_record* records, size_t n, const uint32_t* pkt_len,
+                    const uint32_t* src_labels, int32_t* results);
+
 /* ======================================================================== */
 /* LPM: XDP CIDR prefilter — bpf/bpf_xdp.c:88-184,                           */
 /* pkg/datapath/prefilter/prefilter.go:57-298                                */
@@ -1100,6 +1261,19 @@ int cg_diag_l4_frames_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, cons
                                 const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
                                 const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
                                 int32_t* verdicts, cg_l4_frame_info* info, uint32_t* l4_off);
+/* cg_l4_frames_ct_verdicts_* on the host: the kernel's own walk and lookup
+ * (frame_walk.h, ct_walk.h) over the host copy of the conntrack tables.  No
+ * device, no counters. */
+int cg_diag_l4_frames_ct_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                   const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
+                                   const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                   uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
+                                   cg_ct_record* records, uint32_t* l4_off);
+/* The conntrack tables' own hash of each key (before the bucket mask), and
+ * the built tables' shape: buckets and the recorded probe bound per family
+ * ([0] v4, [1] v6).  For tests that build probe chains. */
+int cg_diag_ct_hash(const cg_ct_key* keys, size_t n, uint32_t* hashes);
+int cg_diag_ct_map_info(uint64_t h, uint32_t ct_id, uint32_t buckets[2], uint32_t probes[2]);
 /* The ipcache tables walked on the host exactly as ipcache_kernel does. */
 int cg_diag_ipcache_eval_host(uint64_t h, uint32_t ipc_id, const uint32_t* v4, size_t n4,
                               cg_remote_endpoint_info* out4, const uint8_t* v6, size_t n6,

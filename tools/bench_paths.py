@@ -290,6 +290,76 @@ def bench_l4_array(torch, dev, stream, cl, args, threads):
                  "mixes": res, "single_map_ceiling_Gtuples_s": ceiling["value"] / 1e9})
 
 
+def _bench_l4_frames_ct(torch, dev, stream, cl, args, arr, kw, raw, off, plen, d_raw, d_off, d_len, d_out, D, n,
+                        sec_plain):
+    """l4_frames_ct_kernel on bench_l4_frames' batch, against a global
+    conntrack map of at least 2^20 keys derived from the frames: of the TCP /
+    UDP frames whose walk completes a third get their reply key (the tuple as
+    loaded), a third their established key (the reversed tuple), a third
+    none; random keys fill the table up to 2^20.  Checked against
+    cg_diag_l4_frames_ct_eval_host over the first copy; timed with and
+    without the 64-byte records."""
+    from cilium_amd import _native as N
+    from cilium_amd.classifier import CT_KEY_DTYPE, CT_RECORD_DTYPE
+    _, winfo, l4o = arr.frame_eval_host_diag(raw, off, pkt_len=plen, info=True, l4_off=True, **kw)
+    proto = winfo["t"]["proto"]
+    sel = np.flatnonzero((winfo["t"]["flags"] != 0) & ((proto == 6) | (proto == 17)))
+    sel = sel[sel % 3 != 2]
+    b = off[:-1].astype(np.int64)[sel]
+    fam = winfo["family"][sel]
+    keys = np.zeros(len(sel), CT_KEY_DTYPE)
+    for f, so, do, size in ((4, 26, 30, 4), (6, 22, 38, 16)):
+        m = fam == f
+        keys["saddr"][m, :size] = raw[b[m][:, None] + np.arange(so, so + size)]
+        keys["daddr"][m, :size] = raw[b[m][:, None] + np.arange(do, do + size)]
+    p = b + l4o[sel]
+    keys["dport"] = raw[p].astype(np.uint16) | raw[p + 1].astype(np.uint16) << 8
+    keys["sport"] = raw[p + 2].astype(np.uint16) | raw[p + 3].astype(np.uint16) << 8
+    keys["nexthdr"], keys["family"] = proto[sel], fam
+    keys["kind"] = np.where(proto[sel] == 6, N.CG_CT_MAP_TCP, N.CG_CT_MAP_ANY)
+    est = sel % 3 == 1  # the reversed tuple: addresses and ports swapped, TUPLE_F_IN
+    rev = keys[est].copy()
+    rev["daddr"], rev["saddr"] = keys["saddr"][est], keys["daddr"][est]
+    rev["dport"], rev["sport"], rev["flags"] = keys["sport"][est], keys["dport"][est], N.CG_TUPLE_F_IN
+    keys[est] = rev
+    keys = np.unique(keys)
+    target = 1 << 20
+    if len(keys) < target:
+        rng = np.random.default_rng(0xC7)
+        fill = np.zeros(target - len(keys), CT_KEY_DTYPE)
+        fill["daddr"][:, :4], fill["saddr"][:, :4] = rng.integers(0, 256, (len(fill), 4)), [172, 31, 0, 0]
+        fill["sport"], fill["nexthdr"], fill["family"] = rng.integers(0, 65536, len(fill)), 6, 4
+        fill["dport"] = np.arange(len(fill)) & 0xFFFF
+        keys = np.unique(np.concatenate([keys, fill]))
+    ct = cl.conntrack_map(max_entries=max(2 * len(keys), target), global_map=True)
+    ct.update(keys)
+    d_rec = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+    arr.frame_verdicts_dev(d_raw, d_off, D, d_out, d_pkt_len=d_len, stream=stream.cuda_stream, conntrack=ct,
+                           d_records=d_rec, **kw)
+    stream.synchronize()
+    want, _, wrec = arr.frame_eval_host_diag(raw, off, pkt_len=plen, info=True, conntrack=ct, **kw)
+    assert np.array_equal(d_out[:D].cpu().numpy(), want), "conntrack frame verdicts differ from the host evaluator"
+    assert d_rec[:D].cpu().numpy().tobytes() == wrec.tobytes(), "conntrack records differ from the host evaluator"
+    sec_rec = timed(torch, stream, lambda: arr.frame_verdicts_dev(
+        d_raw, d_off, n, d_out, d_pkt_len=d_len, stream=stream.cuda_stream, conntrack=ct, d_records=d_rec, **kw),
+        args.steps, 2)
+    del d_rec
+    sec = timed(torch, stream, lambda: arr.frame_verdicts_dev(
+        d_raw, d_off, n, d_out, d_pkt_len=d_len, stream=stream.cuda_stream, conntrack=ct, **kw), args.steps, 2)
+    done = wrec["state"] != 0
+    info = ct.table_info()
+    ct.destroy()
+    return {"kernel": "l4_frames_ct_kernel", "table_keys": int(len(keys)),
+            "table_buckets": {"v4": info[4][0], "v6": info[6][0]}, "table_probe_bound": {"v4": info[4][1], "v6": info[6][1]},
+            "table_bytes": 128 * (info[4][0] + info[6][0]),
+            "state_frac_of_looked_up": {name: float((wrec["state"][done] == s).mean()) for s, name in
+                                        ((1, "new"), (2, "established"), (3, "reply"), (4, "related"))},
+            "looked_up_frac": float(done.mean()),
+            "kernel_ms": sec * 1e3, "Gframes_s": n / sec / 1e9, "over_no_conntrack": sec / sec_plain,
+            "with_records": {"kernel_ms": sec_rec * 1e3, "Gframes_s": n / sec_rec / 1e9,
+                             "over_no_conntrack": sec_rec / sec_plain}}
+
+
 def bench_l4_frames(torch, dev, stream, cl, args, threads):
     """L4 verdicts from raw frames: 256 endpoints' maps (config 2's table mix)
     behind an endpoint map, a 64K-entry ipcache, Ethernet frames snapped to 96
@@ -359,6 +429,8 @@ def bench_l4_frames(torch, dev, stream, cl, args, threads):
     del d_info
     sec = timed(torch, stream, lambda: arr.frame_verdicts_dev(d_raw, d_off, n, d_out, d_pkt_len=d_len,
                                                               stream=stream.cuda_stream, **kw), args.steps, 2)
+    ct_res = _bench_l4_frames_ct(torch, dev, stream, cl, args, arr, kw, raw, off, plen, d_raw, d_off, d_len, d_out, D,
+                                 n, sec)
     # (a) the tuple route over pre-extracted tuples, kernels only
     ran = winfo["t"]["flags"] != 0
     fam4 = ran & (winfo["family"] == 4)
@@ -447,6 +519,7 @@ def bench_l4_frames(torch, dev, stream, cl, args, threads):
                             "policy_verdict_frac": float(ran.mean()), "allowed_frac": float((want >= 0).mean())},
                  "kernel_ms": sec * 1e3, "Gframes_s": n / sec / 1e9,
                  "algorithmic_bytes_per_frame_in": per_frame,
+                 "with_conntrack": ct_res,
                  "tuple_route_ceiling": {"kernel_ms": sec_a * 1e3, "tuples": n_a, "Gtuples_s": n_a / sec_a / 1e9},
                  "from_host_data": {"frames": D, "host_extract_s": t_extract, "tuple_route_wall_s": wall_b,
                                     "frames_wall_s": wall_f, "frames_left_unparsed": int(D - len(plain))}})
