@@ -53,6 +53,10 @@ CG_CT_E_RX_CLOSING, CG_CT_E_TX_CLOSING, CG_CT_E_NAT46, CG_CT_E_LB_LOOPBACK, CG_C
 CG_CT_STATE_NONE, CG_CT_STATE_NEW, CG_CT_STATE_ESTABLISHED, CG_CT_STATE_REPLY, CG_CT_STATE_RELATED = 0, 1, 2, 3, 4
 CG_CT_OP_NONE, CG_CT_OP_CREATE, CG_CT_OP_DELETE = 0, 1, 2
 CG_DROP_CT_CREATE_FAILED = -155
+CG_EPH_F_IPV4, CG_EPH_F_NO_SMAC, CG_EPH_F_NO_DMAC, CG_EPH_F_NO_SIP = 1, 2, 4, 8
+CG_L4_F_WALKED = 0x08
+CG_DROP_INVALID_SMAC, CG_DROP_INVALID_DMAC, CG_DROP_INVALID_SIP = -130, -131, -132
+CG_FRAME_ANSWERED, CG_FRAME_NO_HEADER, CG_FRAME_EFAULT = -3, -4, -14
 
 CG_PF_DYN4, CG_PF_DYN6, CG_PF_FIX4, CG_PF_FIX6 = 1, 2, 4, 8
 CG_XDP_DROP, CG_XDP_PASS = 1, 2
@@ -265,6 +269,16 @@ SIGNATURES = {
                                                 _p]),
     "cg_diag_l4_frames_ct_eval_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _u32, _p, _u32, _p, _u32, _p, _p,
                                                  _p, _p]),
+    "cg_policy_array_set_headers": (C.c_int, [_u64, _u32, _p, _p, _sz]),
+    "cg_policy_array_clear_headers": (C.c_int, [_u64, _u32, _p, _sz]),
+    "cg_policy_array_get_header": (C.c_int, [_u64, _u32, C.c_uint16, _p]),
+    # h, arr, mode, raw, off, n, lxc, labels, ipc, pkt_len, ct, verdicts, info, records [, stream | l4_off]
+    "cg_l4_frames_egress_verdicts_dev": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _p, _u32, _p, _u32, _p, _p, _p,
+                                                   _p]),
+    "cg_l4_frames_egress_verdicts_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _p, _u32, _p, _u32, _p, _p,
+                                                    _p]),
+    "cg_diag_l4_frames_egress_eval_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _p, _u32, _p, _u32, _p, _p,
+                                                     _p, _p]),
     "cg_diag_ct_hash": (C.c_int, [_p, _sz, _p]),
     "cg_diag_ct_map_info": (C.c_int, [_u64, _u32, _p, _p]),
 }

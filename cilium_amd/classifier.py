@@ -58,6 +58,11 @@ CT_ENTRY_DTYPE = np.dtype([("rx_packets", "<u8"), ("rx_bytes", "<u8"), ("tx_pack
 CT_RECORD_DTYPE = np.dtype([("state", "u1"), ("op", "u1"), ("loopback", "u1"), ("pad0", "u1"),
                             ("rev_nat_index", "<u2"), ("pad1", "<u2"), ("pad2", "<u4", (2,)), ("key", CT_KEY_DTYPE),
                             ("pad3", "<u4")])
+# cg_endpoint_header: the from-container program's compile-time constants
+ENDPOINT_HEADER_DTYPE = np.dtype([("lxc_mac", "u1", (6,)), ("node_mac", "u1", (6,)), ("ipv4", "u1", (4,)),
+                                  ("ipv6", "u1", (16,)), ("router_ip6", "u1", (16,)), ("seclabel", "<u4"),
+                                  ("flags", "<u4"), ("pad", "<u4", (2,))])
+assert ENDPOINT_HEADER_DTYPE.itemsize == 64
 assert CT_KEY_DTYPE.itemsize == 44 and CT_ENTRY_DTYPE.itemsize == 56 and CT_RECORD_DTYPE.itemsize == 64
 assert ENDPOINT_KEY_DTYPE.itemsize == 20 and ENDPOINT_INFO_DTYPE.itemsize == 8 and FRAME_INFO_DTYPE.itemsize == 16
 assert L4_TUPLE_DTYPE.itemsize == 12 and KAFKA_REQ_DTYPE.itemsize == 64 and CIDR_DTYPE.itemsize == 20
@@ -739,6 +744,62 @@ class PolicyArray:
         N.check(N.lib.cg_policy_array_get(self.cl.h, self.id, int(lxc[0]), C.byref(v)))
         return v.value or None
 
+    # ------------------------------------- endpoint program headers --
+    @staticmethod
+    def header(*, mac, node_mac, ipv4=None, ipv6=None, router_ip6=None, seclabel: int, verify_smac: bool = True,
+               verify_dmac: bool = True, verify_sip: bool = True) -> np.ndarray:
+        """One ENDPOINT_HEADER_DTYPE record: LXC_MAC, NODE_MAC ("aa:bb:.." or 6
+        bytes), LXC_IPV4 (None: the endpoint has no IPv4 address), LXC_IP,
+        ROUTER_IP, SECLABEL; verify_*=False is DISABLE_*_VERIFICATION."""
+        def mac_bytes(m):
+            b = bytes(int(x, 16) for x in m.split(":")) if isinstance(m, str) else bytes(m)
+            if len(b) != 6:
+                raise ValueError("a MAC address has 6 bytes")
+            return np.frombuffer(b, np.uint8)
+
+        def ip_bytes(a, n):
+            if a is None:
+                return np.zeros(n, np.uint8)
+            b = a if isinstance(a, (bytes, bytearray)) else ipaddress.ip_address(a).packed
+            if len(b) != n:
+                raise ValueError("address of the wrong family")
+            return np.frombuffer(bytes(b), np.uint8)
+
+        h = np.zeros(1, ENDPOINT_HEADER_DTYPE)
+        h["lxc_mac"][0], h["node_mac"][0] = mac_bytes(mac), mac_bytes(node_mac)
+        h["ipv4"][0], h["ipv6"][0], h["router_ip6"][0] = ip_bytes(ipv4, 4), ip_bytes(ipv6, 16), ip_bytes(router_ip6, 16)
+        h["seclabel"] = seclabel
+        h["flags"] = ((N.CG_EPH_F_IPV4 if ipv4 is not None else 0) | (0 if verify_smac else N.CG_EPH_F_NO_SMAC) |
+                      (0 if verify_dmac else N.CG_EPH_F_NO_DMAC) | (0 if verify_sip else N.CG_EPH_F_NO_SIP))
+        return h
+
+    def set_header(self, lxc_id: int, **kw) -> None:
+        """The slot's endpoint program header (see header()); independent of the slot's map."""
+        self.set_headers([lxc_id], self.header(**kw))
+
+    def set_headers(self, lxc_ids, headers: np.ndarray) -> None:
+        """All or nothing (cg_policy_array_set_headers); headers: ENDPOINT_HEADER_DTYPE."""
+        lxc = self._lxc(lxc_ids)
+        hd = np.ascontiguousarray(headers, ENDPOINT_HEADER_DTYPE).reshape(-1)
+        if len(hd) != len(lxc):
+            raise ValueError("one header per lxc_id")
+        N.check(N.lib.cg_policy_array_set_headers(self.cl.h, self.id, _p(lxc) if len(lxc) else None,
+                                                  _p(hd) if len(lxc) else None, len(lxc)))
+
+    def clear_header(self, lxc_id) -> None:
+        lxc = self._lxc(lxc_id)
+        N.check(N.lib.cg_policy_array_clear_headers(self.cl.h, self.id, _p(lxc) if len(lxc) else None, len(lxc)))
+
+    def get_header(self, lxc_id: int) -> Optional[np.ndarray]:
+        """The slot's ENDPOINT_HEADER_DTYPE record, or None when it has none."""
+        lxc = self._lxc(lxc_id)
+        h = np.zeros(1, ENDPOINT_HEADER_DTYPE)
+        rc = N.lib.cg_policy_array_get_header(self.cl.h, self.id, int(lxc[0]), _p(h))
+        if rc == N.CG_NOT_FOUND:
+            return None
+        N.check(rc)
+        return h[0]
+
     def destroy(self) -> None:
         N.check(N.lib.cg_policy_array_destroy(self.cl.h, self.id))
 
@@ -882,6 +943,66 @@ class PolicyArray:
         N.check(N.lib.cg_diag_l4_frames_eval_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep, _p(lab),
                                                   ipc, _p(plen), _p(out), _p(fi), _p(lo)))
         res = (out[:n],) + ((fi[:n],) if info else ()) + ((lo[:n],) if l4_off else ())
+        return res if len(res) > 1 else res[0]
+
+    # --------------------------------------- from raw frames, egress --
+    def _egress_args(self, raw, off, lxc_ids, dst_labels, ipcache, pkt_len, ignore_drop):
+        raw, off, n, lxc, _, lab, ipc, plen, _ = self._frame_args(raw, off, lxc_ids, None, dst_labels, ipcache,
+                                                                  pkt_len, ignore_drop)
+        return raw, off, n, lxc, lab, ipc, plen, N.CG_L4_EGRESS | (N.CG_L4_IGNORE_DROP if ignore_drop else 0)
+
+    def frame_egress_verdicts(self, raw, off, *, lxc_ids, dst_labels=None, ipcache: Optional["IPCache"] = None,
+                              pkt_len=None, ignore_drop: bool = False, info: bool = False,
+                              conntrack: Optional["ConntrackMap"] = None):
+        """The from-container program's verdict per raw Ethernet frame sent by
+        the endpoint in slot lxc_ids[i], which needs a header (set_header):
+        source MAC / gateway MAC / source address checks, the conntrack lookup
+        as CT_EGRESS, policy_can_egress on the destination identity
+        (dst_labels, or the ipcache resolution of the destination address),
+        one launch (cg_l4_frames_egress_verdicts_host).  Returns as
+        frame_verdicts does: info=True adds the FRAME_INFO records and, with
+        conntrack, the CT_RECORD_DTYPE records ConntrackMap.apply takes."""
+        raw, off, n, lxc, lab, ipc, plen, mode = self._egress_args(raw, off, lxc_ids, dst_labels, ipcache, pkt_len,
+                                                                   ignore_drop)
+        out = np.zeros(max(n, 1), np.int32)
+        fi = np.zeros(max(n, 1), FRAME_INFO_DTYPE) if info else None
+        rec = np.zeros(max(n, 1), CT_RECORD_DTYPE) if info and conntrack is not None else None
+        N.check(N.lib.cg_l4_frames_egress_verdicts_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc),
+                                                        _p(lab), ipc, _p(plen),
+                                                        conntrack.id if conntrack is not None else 0, _p(out),
+                                                        _p(fi), _p(rec)))
+        if not info:
+            return out[:n]
+        return (out[:n], fi[:n], rec[:n]) if conntrack is not None else (out[:n], fi[:n])
+
+    def frame_egress_verdicts_dev(self, d_raw, d_off, n: int, d_out, *, d_lxc_ids, d_dst_labels=None,
+                                  ipcache: Optional["IPCache"] = None, d_pkt_len=None, ignore_drop: bool = False,
+                                  d_info=None, stream=None, conntrack: Optional["ConntrackMap"] = None,
+                                  d_records=None) -> None:
+        """Device buffers as frame_verdicts_dev takes them, async on `stream`."""
+        mode = N.CG_L4_EGRESS | (N.CG_L4_IGNORE_DROP if ignore_drop else 0)
+        N.check(N.lib.cg_l4_frames_egress_verdicts_dev(
+            self.cl.h, self.id, mode, _p(d_raw), _p(d_off), n, _p(d_lxc_ids), _p(d_dst_labels),
+            ipcache.id if ipcache is not None else 0, _p(d_pkt_len), conntrack.id if conntrack is not None else 0,
+            _p(d_out), _p(d_info), _p(d_records), stream))
+
+    def frame_egress_eval_host_diag(self, raw, off, *, lxc_ids, dst_labels=None, ipcache: Optional["IPCache"] = None,
+                                    pkt_len=None, ignore_drop: bool = False, info: bool = False,
+                                    l4_off: bool = False, conntrack: Optional["ConntrackMap"] = None):
+        """Diagnostics only: frame_egress_verdicts by the kernel's own walk on
+        the CPU (no device, no counters).  l4_off=True appends the L4 offsets."""
+        raw, off, n, lxc, lab, ipc, plen, mode = self._egress_args(raw, off, lxc_ids, dst_labels, ipcache, pkt_len,
+                                                                   ignore_drop)
+        out = np.zeros(max(n, 1), np.int32)
+        fi = np.zeros(max(n, 1), FRAME_INFO_DTYPE) if info else None
+        rec = np.zeros(max(n, 1), CT_RECORD_DTYPE) if info and conntrack is not None else None
+        lo = np.zeros(max(n, 1), np.uint32) if l4_off else None
+        N.check(N.lib.cg_diag_l4_frames_egress_eval_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc),
+                                                         _p(lab), ipc, _p(plen),
+                                                         conntrack.id if conntrack is not None else 0, _p(out),
+                                                         _p(fi), _p(rec), _p(lo)))
+        res = (out[:n],) + ((fi[:n],) if info else ()) + ((rec[:n],) if rec is not None else ()) + \
+            ((lo[:n],) if l4_off else ())
         return res if len(res) > 1 else res[0]
 
 

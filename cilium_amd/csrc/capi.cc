@@ -16,6 +16,7 @@
 #include "ct_map.h"
 #include "endpoint_map.h"
 #include "engine.h"
+#include "egress_walk.h"
 #include "frame_walk.h"
 #include "http.h"
 #include "kafka.h"
@@ -616,6 +617,47 @@ int cg_policy_array_get(uint64_t h, uint32_t arr_id, uint16_t lxc_id, uint32_t* 
   });
 }
 
+// Endpoint program headers: the from-container program's compile-time
+// constants per slot (l4_array.h), independent of the slots' maps.
+int cg_policy_array_set_headers(uint64_t h, uint32_t arr_id, const uint16_t* lxc_ids,
+                                const cg_endpoint_header* headers, size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    PolicyArrayState& a = get_arr(*e, arr_id);
+    if (n && (!lxc_ids || !headers)) fail(CG_INVALID_ARGUMENT, "NULL lxc_ids/headers");
+    constexpr uint32_t known = CG_EPH_F_IPV4 | CG_EPH_F_NO_SMAC | CG_EPH_F_NO_DMAC | CG_EPH_F_NO_SIP;
+    for (size_t i = 0; i < n; ++i) {  // all checked before any header changes
+      if (headers[i].flags & ~known) fail(CG_INVALID_ARGUMENT, "unknown endpoint header flags");
+      if (headers[i].pad[0] | headers[i].pad[1]) fail(CG_INVALID_ARGUMENT, "endpoint header pad must be 0");
+    }
+    for (size_t i = 0; i < n; ++i) a.headers[lxc_ids[i]] = headers[i];
+    if (n) a.headers_changed = true;
+  });
+}
+
+int cg_policy_array_clear_headers(uint64_t h, uint32_t arr_id, const uint16_t* lxc_ids, size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    PolicyArrayState& a = get_arr(*e, arr_id);
+    if (n && !lxc_ids) fail(CG_INVALID_ARGUMENT, "NULL lxc_ids");
+    for (size_t i = 0; i < n; ++i) a.headers_changed |= a.headers.erase(lxc_ids[i]) != 0;
+  });
+}
+
+int cg_policy_array_get_header(uint64_t h, uint32_t arr_id, uint16_t lxc_id, cg_endpoint_header* out) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    PolicyArrayState& a = get_arr(*e, arr_id);
+    if (!out) fail(CG_INVALID_ARGUMENT, "out is NULL");
+    auto it = a.headers.find(lxc_id);
+    if (it == a.headers.end()) fail(CG_NOT_FOUND, "policy array: the slot has no header");
+    *out = it->second;
+  });
+}
+
 // One snapshot of the whole array, taken under the handle lock: dirty members
 // are rebuilt, and the slot words and records are uploaded again only if a
 // slot or a member's published tables changed since the last upload.  The
@@ -962,9 +1004,15 @@ int cg_ct_map_apply(uint64_t h, uint32_t ct_id, const cg_ct_record* records, siz
         continue;
       }
       cg_ct_entry en{};
-      en.rx_packets = 1;
-      en.rx_bytes = pkt_len ? pkt_len[i] : 0;
-      en.src_sec_id = src_labels ? src_labels[i] : 0;
+      if (r.pad0 == 1) {  // dir == CT_EGRESS (conntrack.h:706-712): tx, and SECLABEL from the record
+        en.tx_packets = 1;
+        en.tx_bytes = pkt_len ? pkt_len[i] : 0;
+        en.src_sec_id = r.pad2[0];
+      } else {
+        en.rx_packets = 1;
+        en.rx_bytes = pkt_len ? pkt_len[i] : 0;
+        en.src_sec_id = src_labels ? src_labels[i] : 0;
+      }
       p.entries[k] = en;
       en.flags |= CG_CT_E_SEEN_NON_SYN;
       p.entries[kr] = en;
@@ -1075,32 +1123,28 @@ int cg_l4_frames_ct_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, con
 
 static void* stage_in(StagingSlot& sl, int i, const void* src, size_t bytes);
 
-static void frames_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw, const uint64_t* raw_off,
-                        size_t n, const uint16_t* lxc_ids, uint32_t ep_id, const uint32_t* src_labels,
-                        uint32_t ipc_id, const uint32_t* pkt_len, const uint32_t* ct_id, int32_t* verdicts,
-                        cg_l4_frame_info* info, cg_ct_record* recs) {
-  auto e = get(h);
-  check_frames_args(mode, lxc_ids, ep_id, src_labels, ipc_id);
-  e->require_gpu();
-  if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
+// The host entries' staging: the blob's window [raw_off[0], raw_off[n]), the offsets and the per-frame inputs go
+// up, launch(d_raw, d_off, d_lxc, d_labels, d_len, d_out, d_info, d_recs, stream) runs, the results come back.
+using FramesLaunch = std::function<void(const uint8_t*, const uint64_t*, const uint16_t*, const uint32_t*,
+                                        const uint32_t*, int32_t*, void*, void*, void*)>;
+static void frames_staged(Engine& e, const uint8_t* raw, const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids,
+                          const uint32_t* labels, const uint32_t* pkt_len, int32_t* verdicts, cg_l4_frame_info* info,
+                          cg_ct_record* recs, const FramesLaunch& launch) {
   const uint64_t lo = raw_off[0], bytes = raw_off[n] > lo ? raw_off[n] - lo : 0;
-  if (bytes && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
-  const FramesView v = frames_view(*e, arr_id, ep_id, ipc_id, ct_id);
-  if (!n) return;
-  e->set_device();
-  auto lease = e->staging.acquire(e->device);
+  e.set_device();
+  auto lease = e.staging.acquire(e.device);
   const auto st = (hipStream_t)lease->stream;
-  // the blob's window [raw_off[0], raw_off[n]) is what travels; the kernel adds the offsets to d_raw
+  // the kernel adds the offsets to d_raw
   const uint8_t* d_win = (const uint8_t*)stage_in(*lease, 0, raw + lo, bytes);
   const uint8_t* d_raw = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(d_win) - lo);
   const uint64_t* d_off = (const uint64_t*)stage_in(*lease, 1, raw_off, (n + 1) * 8);
   const uint16_t* d_lxc = lxc_ids ? (const uint16_t*)stage_in(*lease, 2, lxc_ids, n * 2) : nullptr;
-  const uint32_t* d_lab = src_labels ? (const uint32_t*)stage_in(*lease, 3, src_labels, n * 4) : nullptr;
+  const uint32_t* d_lab = labels ? (const uint32_t*)stage_in(*lease, 3, labels, n * 4) : nullptr;
   const uint32_t* d_len = pkt_len ? (const uint32_t*)stage_in(*lease, 4, pkt_len, n * 4) : nullptr;
   int32_t* d_out = (int32_t*)lease->dev_buf(5, n * 4);
   void* d_info = info ? lease->dev_buf(6, n * sizeof(cg_l4_frame_info)) : nullptr;
   void* d_recs = recs ? lease->dev_buf(7, n * sizeof(cg_ct_record)) : nullptr;
-  frames_launch(*e, v, mode, d_raw, d_off, n, d_lxc, d_lab, d_len, d_out, d_info, d_recs, st);
+  launch(d_raw, d_off, d_lxc, d_lab, d_len, d_out, d_info, d_recs, (void*)st);
   int32_t* h_out = (int32_t*)lease->host_buf(5, n * 4);
   hip_check(hipMemcpyAsync(h_out, d_out, n * 4, hipMemcpyDeviceToHost, st), "D2H");
   void* h_info = info ? lease->host_buf(6, n * sizeof(cg_l4_frame_info)) : nullptr;
@@ -1111,6 +1155,24 @@ static void frames_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_
   memcpy(verdicts, h_out, n * 4);
   if (info) memcpy(info, h_info, n * sizeof(cg_l4_frame_info));
   if (recs) memcpy(recs, h_recs, n * sizeof(cg_ct_record));
+}
+
+static void frames_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw, const uint64_t* raw_off,
+                        size_t n, const uint16_t* lxc_ids, uint32_t ep_id, const uint32_t* src_labels,
+                        uint32_t ipc_id, const uint32_t* pkt_len, const uint32_t* ct_id, int32_t* verdicts,
+                        cg_l4_frame_info* info, cg_ct_record* recs) {
+  auto e = get(h);
+  check_frames_args(mode, lxc_ids, ep_id, src_labels, ipc_id);
+  e->require_gpu();
+  if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
+  if (raw_off[n] > raw_off[0] && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
+  const FramesView v = frames_view(*e, arr_id, ep_id, ipc_id, ct_id);
+  if (!n) return;
+  frames_staged(*e, raw, raw_off, n, lxc_ids, src_labels, pkt_len, verdicts, info, recs,
+                [&](const uint8_t* d_raw, const uint64_t* d_off, const uint16_t* d_lxc, const uint32_t* d_lab,
+                    const uint32_t* d_len, int32_t* d_out, void* d_info, void* d_recs, void* st) {
+                  frames_launch(*e, v, mode, d_raw, d_off, n, d_lxc, d_lab, d_len, d_out, d_info, d_recs, st);
+                });
 }
 
 int cg_l4_frames_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
@@ -1130,6 +1192,109 @@ int cg_l4_frames_ct_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, co
   return guarded([&] {
     frames_host(h, arr_id, mode, raw, raw_off, n, lxc_ids, ep_id, src_labels, ipc_id, pkt_len, &ct_id, verdicts, info,
                 records);
+  });
+}
+
+// ------------------------------------- L4 verdicts from frames, egress ----
+// One snapshot of the array with its headers, the ipcache and the conntrack
+// map, taken under one hold of the handle lock; the launch holds all of them.
+struct EgressView {
+  L4ArrView arr;
+  std::shared_ptr<DevTables> hdr_keep, ipc_keep, ct_keep;
+  EpHdrDev hdr{};
+  IpcacheDev ipc{};
+  CtMapDev ct{};
+};
+static void check_egress_args(uint32_t mode, const void* lxc, const void* labels, uint32_t ipc_id, uint32_t ct_id,
+                              const void* recs) {
+  if ((mode & ~CG_L4_IGNORE_DROP) != CG_L4_EGRESS)
+    fail(CG_INVALID_ARGUMENT, "egress frame verdicts run the from-container program: mode is CG_L4_EGRESS [| CG_L4_IGNORE_DROP]");
+  if (!lxc) fail(CG_INVALID_ARGUMENT, "lxc_ids is mandatory: the program hangs on the endpoint's own device");
+  if ((labels != nullptr) == (ipc_id != 0))
+    fail(CG_INVALID_ARGUMENT, "give dst_labels or an ipcache, not both or neither");
+  if (recs && !ct_id) fail(CG_INVALID_ARGUMENT, "records need a conntrack map");
+}
+static EgressView egress_view(Engine& e, uint32_t arr_id, uint32_t ipc_id, uint32_t ct_id) {
+  std::lock_guard<std::mutex> lk(e.mu);
+  EgressView v;
+  if (ct_id) {
+    CtMapState& p = get_ct(e, ct_id);
+    if (p.dirty) p.rebuild(e);
+    v.ct_keep = p.tab;
+    v.ct = p.dev;
+  }
+  v.arr = l4_array_view_locked(e, arr_id);
+  PolicyArrayState& a = get_arr(e, arr_id);
+  if (a.headers_changed || !a.hdr_tab) {
+    std::vector<uint32_t> idx;
+    std::vector<uint4> recs;
+    a.header_tables(&idx, &recs);
+    e.set_device();
+    auto t = std::make_shared<DevTables>();
+    EpHdrDev d{};
+    d.idx = t->add(idx);
+    d.recs = t->add(recs);
+    a.hdr_tab = std::move(t);  // publish
+    a.hdr_dev = d;
+    a.headers_changed = false;
+  }
+  v.hdr_keep = a.hdr_tab;
+  v.hdr = a.hdr_dev;
+  if (ipc_id) {
+    IpcacheState& p = get_ipc(e, ipc_id);
+    if (p.dirty) p.rebuild(e);
+    v.ipc_keep = p.tab;
+    v.ipc = p.dev;
+  }
+  return v;
+}
+static void egress_launch(Engine& e, const EgressView& v, uint32_t mode, const uint8_t* d_raw, const uint64_t* d_off,
+                          size_t n, const uint16_t* d_lxc, const uint32_t* d_labels, const uint32_t* d_len,
+                          int32_t* d_out, void* d_info, void* d_recs, void* st) {
+  check_launch(launch_l4_frames_egress(v.arr.dev, v.hdr, v.ipc_keep ? &v.ipc : nullptr, v.ct_keep ? &v.ct : nullptr,
+                                       d_raw, d_off, n, d_lxc, d_labels, d_len, d_out, d_info, d_recs, mode, st, e.cus),
+               "l4 frames egress kernel launch");
+  fence(v.ct_keep, st);
+  v.arr.keep->own.fence.record(st);
+  fence(v.hdr_keep, st);
+  fence(v.ipc_keep, st);
+}
+
+int cg_l4_frames_egress_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
+                                     const uint64_t* d_raw_off, size_t n, const uint16_t* d_lxc_ids,
+                                     const uint32_t* d_dst_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
+                                     uint32_t ct_id, int32_t* d_verdicts, cg_l4_frame_info* d_info,
+                                     cg_ct_record* d_records, void* stream) {
+  return guarded([&] {
+    auto e = get(h);
+    check_egress_args(mode, d_lxc_ids, d_dst_labels, ipc_id, ct_id, d_records);
+    e->require_gpu();
+    if (!d_raw_off || (n && !d_verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
+    const EgressView v = egress_view(*e, arr_id, ipc_id, ct_id);
+    e->set_device();
+    egress_launch(*e, v, mode, d_raw, d_raw_off, n, d_lxc_ids, d_dst_labels, d_pkt_len, d_verdicts, d_info, d_records,
+                  stream_of(*e, stream));
+  });
+}
+
+int cg_l4_frames_egress_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                      const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids,
+                                      const uint32_t* dst_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                      uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
+                                      cg_ct_record* recs) {
+  return guarded([&] {
+    auto e = get(h);
+    check_egress_args(mode, lxc_ids, dst_labels, ipc_id, ct_id, recs);
+    e->require_gpu();
+    if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
+    if (raw_off[n] > raw_off[0] && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
+    const EgressView v = egress_view(*e, arr_id, ipc_id, ct_id);
+    if (!n) return;
+    frames_staged(*e, raw, raw_off, n, lxc_ids, dst_labels, pkt_len, verdicts, info, recs,
+                  [&](const uint8_t* d_raw, const uint64_t* d_off, const uint16_t* d_lxc, const uint32_t* d_lab,
+                      const uint32_t* d_len, int32_t* d_out, void* d_info, void* d_recs, void* st) {
+                    egress_launch(*e, v, mode, d_raw, d_off, n, d_lxc, d_lab, d_len, d_out, d_info, d_recs, st);
+                  });
   });
 }
 
@@ -2940,6 +3105,26 @@ int cg_diag_l4_array_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const
   });
 }
 
+// The array as the frames kernels see it, over the members' host views (the caller holds e.mu): slot words, and
+// one record per member map.
+struct L4ArrHostView {
+  std::vector<uint32_t> slot = std::vector<uint32_t>(CG_POLICY_ARRAY_SLOTS, 0u);
+  std::vector<L4Dev> recs;
+  L4ArrHostView(Engine& e, PolicyArrayState& a) {
+    std::map<uint32_t, uint32_t> word;
+    for (const auto& ref : a.refs) {
+      PolicyMapState& m = get_map(e, ref.first);
+      if (m.dirty) m.rebuild(e);
+      word.emplace(ref.first, (uint32_t)recs.size() + 1);
+      recs.push_back(m.host_view());
+    }
+    for (uint32_t s = 0; s < CG_POLICY_ARRAY_SLOTS; ++s)
+      if (a.slot_map[s]) slot[s] = word[a.slot_map[s]];
+    if (recs.empty()) recs.push_back(L4Dev{});
+  }
+  L4ArrDev dev() const { return L4ArrDev{slot.data(), recs.data()}; }
+};
+
 // Per frame as l4_frames_kernel does it: frame_walk.h over the host views of
 // the array, the endpoint map and the ipcache.  No device, no counters.
 // l4_off (may be NULL): the L4 offset the walk found, 0 where it did not get
@@ -2957,20 +3142,8 @@ static void frames_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const u
   if (whi > wlo && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
   std::lock_guard<std::mutex> lk(e->mu);
   PolicyArrayState& a = get_arr(*e, arr_id);
-  // the array as the kernel sees it: slot words over the members' host views
-  std::map<uint32_t, uint32_t> word;
-  std::vector<L4Dev> recs;
-  for (const auto& ref : a.refs) {
-    PolicyMapState& m = get_map(*e, ref.first);
-    if (m.dirty) m.rebuild(*e);
-    word.emplace(ref.first, (uint32_t)recs.size() + 1);
-    recs.push_back(m.host_view());
-  }
-  std::vector<uint32_t> slot(CG_POLICY_ARRAY_SLOTS, 0u);
-  for (uint32_t s = 0; s < CG_POLICY_ARRAY_SLOTS; ++s)
-    if (a.slot_map[s]) slot[s] = word[a.slot_map[s]];
-  if (recs.empty()) recs.push_back(L4Dev{});
-  const L4ArrDev A{slot.data(), recs.data()};
+  const L4ArrHostView av(*e, a);
+  const L4ArrDev A = av.dev();
   EpMapDev E{};
   IpcacheDev ipc{};
   if (ep_id) {
@@ -3049,6 +3222,72 @@ int cg_diag_l4_frames_ct_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, c
   return guarded([&] {
     frames_eval_host(h, arr_id, mode, raw, raw_off, n, lxc_ids, ep_id, src_labels, ipc_id, pkt_len, &ct_id, verdicts,
                      info, records, l4_off);
+  });
+}
+
+// Per frame as l4_frames_egress_kernel does it: egress_walk.h over the host
+// views of the array, its headers, the ipcache and the conntrack map.
+int cg_diag_l4_frames_egress_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                       const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids,
+                                       const uint32_t* dst_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                       uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
+                                       cg_ct_record* ct_recs, uint32_t* l4_off) {
+  return guarded([&] {
+    auto e = get(h);
+    check_egress_args(mode, lxc_ids, dst_labels, ipc_id, ct_id, ct_recs);
+    if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
+    const uint64_t wlo = raw_off[0], whi = raw_off[n];
+    if (whi > wlo && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
+    std::lock_guard<std::mutex> lk(e->mu);
+    PolicyArrayState& a = get_arr(*e, arr_id);
+    const L4ArrHostView av(*e, a);
+    const L4ArrDev A = av.dev();
+    std::vector<uint32_t> hidx;
+    std::vector<uint4> hrecs;
+    a.header_tables(&hidx, &hrecs);
+    const EpHdrDev H{hidx.data(), hrecs.data()};
+    IpcacheDev ipc{};
+    if (ipc_id) {
+      IpcacheState& p = get_ipc(*e, ipc_id);
+      if (p.dirty) p.rebuild(*e);
+      ipc = p.host_view();
+    }
+    CtMapDev C{};
+    if (ct_id) {
+      CtMapState& p = get_ct(*e, ct_id);
+      if (p.dirty) p.rebuild(*e);
+      C = p.host_view();
+    }
+    const uint8_t* lo = raw + wlo;
+    const uint8_t* hi = whi > wlo ? raw + whi : lo;
+    for (size_t i = 0; i < n; ++i) {
+      uint64_t start;
+      const uint32_t len = frame_range(raw_off[i], raw_off[i + 1], wlo, whi, &start);
+      const uint8_t* base = raw + start;
+      auto ld = [&](uint32_t o) {
+        uint32_t v = 0;
+        for (int k = 0; k < 4; ++k) {
+          const uint8_t* p = base + o + k;
+          if (p >= lo && p < hi) v |= (uint32_t)*p << (8 * k);
+        }
+        return v;
+      };
+      auto count = [](const L4Dev&, uint32_t) {};
+      const uint32_t plen = pkt_len ? pkt_len[i] : len;
+      const uint32_t lxc = lxc_ids[i], label = dst_labels ? dst_labels[i] : 0u;
+      cg_l4_frame_info fi;
+      CtRecWords r;
+      uint32_t lo4 = 0;
+      int32_t v;
+      if (ct_id && ipc_id) v = egress_verdict<true, true>(A, H, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
+      else if (ct_id) v = egress_verdict<false, true>(A, H, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
+      else if (ipc_id) v = egress_verdict<true, false>(A, H, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
+      else v = egress_verdict<false, false>(A, H, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
+      verdicts[i] = v;
+      if (info) info[i] = fi;
+      if (ct_recs) memcpy(&ct_recs[i], r.w, sizeof(cg_ct_record));
+      if (l4_off) l4_off[i] = lo4;
+    }
   });
 }
 

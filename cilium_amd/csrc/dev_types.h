@@ -114,6 +114,16 @@ struct L4ArrDev {
   const L4Dev* recs;     // one per member map
 };
 static_assert(sizeof(L4Dev) == 32, "the array kernel reads a record as two 16-byte loads");
+// The array's endpoint program headers (cg_endpoint_header), read by the egress
+// frames kernel only: one word per slot, 0 for a slot without a header, else
+// 1 + the index of its 64-byte record (four 16-byte loads).  Kept beside
+// L4ArrDev, not in it, so the array and ingress kernels' arguments stay as
+// they are.
+struct EpHdrDev {
+  const uint32_t* idx;  // CG_POLICY_ARRAY_SLOTS words
+  const uint4* recs;    // 4 per header
+};
+static_assert(sizeof(cg_endpoint_header) == 64, "a header is four 16-byte loads");
 
 // ----------------------------------------------------------------- LPM ----
 // IPv4: two levels of 2-bit codes (0 not covered, 1 covered, 2 mixed/partial),

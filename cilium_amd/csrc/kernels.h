@@ -37,6 +37,13 @@ int launch_l4_frames_ct(const L4ArrDev& A, const EpMapDev* E, const IpcacheDev* 
                         const uint8_t* raw, const uint64_t* off, size_t n, const uint16_t* lxc, const uint32_t* labels,
                         const uint32_t* pkt_len, int32_t* out, void* info, void* recs, uint32_t mode, void* stream,
                         int cus);
+// The from-container program per frame (egress_walk.h): lxc is mandatory, H the
+// array's endpoint headers; ipc NULL: labels are the destination identities;
+// C NULL: no conntrack map (recs is then not written).
+int launch_l4_frames_egress(const L4ArrDev& A, const EpHdrDev& H, const IpcacheDev* ipc, const CtMapDev* C,
+                            const uint8_t* raw, const uint64_t* off, size_t n, const uint16_t* lxc,
+                            const uint32_t* labels, const uint32_t* pkt_len, int32_t* out, void* info, void* recs,
+                            uint32_t mode, void* stream, int cus);
 int launch_lpm(const LpmDev& t, bool v4_filter, bool v6_filter, const uint32_t* v4, size_t n4,
                uint8_t* out4, const uint8_t* v6, size_t n6, uint8_t* out6, void* stream, int cus);
 // order (optional): out[order[slot]] instead of out[slot] (request order;

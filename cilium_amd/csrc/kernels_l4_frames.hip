@@ -8,7 +8,8 @@
 // endpoint map and the ipcache as its frame asks, and walks the slot's map as
 // l4_array_kernel does.  Counters go to the selected map's own array.
 // l4_frames_ct_kernel is the same lane per frame with the conntrack lookup of
-// ct_walk.h between the walk and the verdict.
+// ct_walk.h between the walk and the verdict.  l4_frames_egress_kernel runs
+// the endpoint's from-container program (egress_walk.h) the same way.
 #include <hip/hip_runtime.h>
 
 #include <map>
@@ -17,6 +18,7 @@
 #include "../../include/cilium_gpu.h"
 #include "ct_walk.h"
 #include "dev_types.h"
+#include "egress_walk.h"
 #include "frame_walk.h"
 #include "kernels.h"
 
@@ -180,7 +182,85 @@ int launch_ct_t(const L4ArrDev& A, const EpMapDev& E, const IpcacheDev& ipc, con
   return (int)hipGetLastError();
 }
 
+
+// The from-container program (egress_walk.h): the same lane per frame.  The
+// endpoint's 64-byte header comes as four 16-byte loads (a batch touches few
+// distinct headers: they sit in L2), the MACs are compared as the frame's
+// first three words.  kCt: the conntrack lookup and a record per frame.
+template <bool kIpc, bool kCt>
+__global__ __launch_bounds__(kFrmThreads) void l4_frames_egress_kernel(
+    L4ArrDev A, EpHdrDev H, IpcacheDev ipc, CtMapDev C, const uint8_t* __restrict__ raw,
+    const uint64_t* __restrict__ off, size_t n, const uint16_t* __restrict__ lxc, const uint32_t* __restrict__ labels,
+    const uint32_t* __restrict__ pkt_len, int32_t* __restrict__ out, uint4* __restrict__ info,
+    uint4* __restrict__ recs, uint32_t mode) {
+  const uint64_t wlo = off[0], whi = off[n];
+  const uint8_t* lo = raw + wlo;
+  const uint8_t* hi = whi > wlo ? raw + whi : lo;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    uint64_t start;
+    const uint32_t len = frame_range(off[i], off[i + 1], wlo, whi, &start);
+    const uint8_t* base = raw + start;
+    const uint32_t plen = pkt_len ? __builtin_nontemporal_load(pkt_len + i) : len;
+    const uint32_t id = (uint32_t)__builtin_nontemporal_load(lxc + i);
+    const uint32_t label = kIpc ? 0u : __builtin_nontemporal_load(labels + i);
+    cg_l4_frame_info fi;
+    CtRecWords r;
+    uint32_t l4_off;
+    const int32_t v = egress_verdict<kIpc, kCt>(
+        A, H, ipc, C, [&](uint32_t o) { return frame_word(base + o, lo, hi); }, len, id, label, plen, mode, &fi,
+        &l4_off, &r, [&](const L4Dev& t, uint32_t entry) {
+          atomicAdd(&t.counters[2 * entry], 1ULL);
+          atomicAdd(&t.counters[2 * entry + 1], (unsigned long long)plen);
+        });
+    __builtin_nontemporal_store(v, out + i);
+    if (info) {
+      uint4 q;
+      q.x = fi.t.identity;
+      q.y = (uint32_t)fi.t.dport | (uint32_t)fi.t.proto << 16 | (uint32_t)fi.t.flags << 24;
+      q.z = fi.t.len;
+      q.w = (uint32_t)fi.lxc_id | (uint32_t)fi.family << 16;
+      info[i] = q;
+    }
+    if (kCt && recs) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        recs[4 * i + q] = make_uint4(r.w[4 * q], r.w[4 * q + 1], r.w[4 * q + 2], r.w[4 * q + 3]);
+    }
+  }
+}
+
+template <bool kIpc, bool kCt>
+int launch_egress_t(const L4ArrDev& A, const EpHdrDev& H, const IpcacheDev& ipc, const CtMapDev& C, const uint8_t* raw,
+                    const uint64_t* off, size_t n, const uint16_t* lxc, const uint32_t* labels,
+                    const uint32_t* pkt_len, int32_t* out, void* info, void* recs, uint32_t mode, void* stream,
+                    int cus) {
+  size_t need = (n + kFrmThreads - 1) / kFrmThreads;
+  const size_t cap = (size_t)cus * resident_blocks((const void*)l4_frames_egress_kernel<kIpc, kCt>);
+  if (need > cap) need = cap;
+  hipLaunchKernelGGL((l4_frames_egress_kernel<kIpc, kCt>), dim3((unsigned)need), dim3(kFrmThreads), 0,
+                     (hipStream_t)stream, A, H, ipc, C, raw, off, n, lxc, labels, pkt_len, out, (uint4*)info,
+                     (uint4*)recs, mode);
+  return (int)hipGetLastError();
+}
+
 }  // namespace
+
+int launch_l4_frames_egress(const L4ArrDev& A, const EpHdrDev& H, const IpcacheDev* ipc, const CtMapDev* C,
+                            const uint8_t* raw, const uint64_t* off, size_t n, const uint16_t* lxc,
+                            const uint32_t* labels, const uint32_t* pkt_len, int32_t* out, void* info, void* recs,
+                            uint32_t mode, void* stream, int cus) {
+  if (n == 0) return 0;
+  const IpcacheDev c = ipc ? *ipc : IpcacheDev{};
+  const CtMapDev m = C ? *C : CtMapDev{};
+  if (ipc && C)
+    return launch_egress_t<true, true>(A, H, c, m, raw, off, n, lxc, labels, pkt_len, out, info, recs, mode, stream, cus);
+  if (ipc)
+    return launch_egress_t<true, false>(A, H, c, m, raw, off, n, lxc, labels, pkt_len, out, info, recs, mode, stream, cus);
+  if (C)
+    return launch_egress_t<false, true>(A, H, c, m, raw, off, n, lxc, labels, pkt_len, out, info, recs, mode, stream, cus);
+  return launch_egress_t<false, false>(A, H, c, m, raw, off, n, lxc, labels, pkt_len, out, info, recs, mode, stream, cus);
+}
 
 int launch_l4_frames_ct(const L4ArrDev& A, const EpMapDev* E, const IpcacheDev* ipc, const CtMapDev& C,
                         const uint8_t* raw, const uint64_t* off, size_t n, const uint16_t* lxc, const uint32_t* labels,

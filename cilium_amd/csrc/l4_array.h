@@ -29,6 +29,28 @@ struct PolicyArrayState {
   std::shared_ptr<L4ArrTables> tab;  // the published upload
   L4ArrDev dev{};                    // view of tab; copy it together with tab
 
+  // Endpoint program headers (cg_endpoint_header), independent of the slots'
+  // maps.  Their upload is a table set of its own, built when an egress call
+  // first asks for it and after every change, under the same hold of the
+  // handle lock that takes the array's snapshot; a launch holds both.
+  std::map<uint16_t, cg_endpoint_header> headers;
+  bool headers_changed = true;
+  std::shared_ptr<DevTables> hdr_tab;
+  EpHdrDev hdr_dev{};
+
+  // The headers as the egress kernel reads them (dev_types.h EpHdrDev).
+  void header_tables(std::vector<uint32_t>* idx, std::vector<uint4>* recs) const {
+    idx->assign(CG_POLICY_ARRAY_SLOTS, 0u);
+    recs->clear();
+    for (const auto& kv : headers) {
+      (*idx)[kv.first] = (uint32_t)(recs->size() / 4) + 1;
+      uint4 w[4];
+      memcpy(w, &kv.second, sizeof(w));
+      recs->insert(recs->end(), w, w + 4);
+    }
+    if (recs->empty()) recs->resize(4);  // never read: every index word is 0
+  }
+
   void put(uint32_t lxc_id, uint32_t map_id) {  // map_id 0 empties the slot
     uint32_t& s = slot_map[lxc_id];
     if (s == map_id) return;

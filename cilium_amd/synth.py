@@ -826,3 +826,55 @@ def l4_frames(n: int, dst4: np.ndarray, dst6: np.ndarray, src4: np.ndarray, src6
     off = np.zeros(n + 1, np.uint64)
     np.cumsum(cap, out=off[1:])
     return raw, off, wire.astype(np.uint32)
+
+
+def l4_egress_frames(n: int, lxc_ids: np.ndarray, headers: np.ndarray, dst4: np.ndarray, dst6: np.ndarray,
+                     dports_be: np.ndarray, seed: int = SEED, bad_share: float = 0.06, **kw):
+    """Ethernet frames for PolicyArray.frame_egress_verdicts: (raw, off,
+    pkt_len, lxc_ids per frame).
+
+    The frames are l4_frames' (same mix, options, extension chains, truncation;
+    **kw goes there), each then sent by one endpoint of the pool: lxc_ids[j]
+    with headers[j] (ENDPOINT_HEADER_DTYPE) gives frame bytes 0..5 = node_mac,
+    6..11 = lxc_mac and the IP source address = the header's ipv4 / ipv6, as
+    far as the captured bytes reach.  bad_share of the frames then get one of
+    the three wrong (a flipped bit in the source MAC, the destination MAC or
+    the source address), a third each.  Destinations come from dst4 / dst6."""
+    from .classifier import ENDPOINT_HEADER_DTYPE
+    lxc_ids = np.ascontiguousarray(lxc_ids, np.uint16).reshape(-1)
+    headers = np.ascontiguousarray(headers, ENDPOINT_HEADER_DTYPE).reshape(-1)
+    if len(lxc_ids) != len(headers) or not len(headers):
+        raise ValueError("one header per lxc id, at least one")
+    zero4, zero6 = np.zeros((1, 4), np.uint8), np.zeros((1, 16), np.uint8)
+    raw, off, wire = l4_frames(n, dst4, dst6, zero4, zero6, dports_be, seed=seed, **kw)
+    raw = raw.copy()
+    rng = np.random.default_rng(seed ^ 0xE6E5)
+    pick = rng.integers(0, len(headers), n)
+    start = off[:-1].astype(np.int64)
+    cap = np.diff(off.astype(np.int64))
+
+    def write(sel, at, vals):  # vals: (n, k) bytes for every frame; written where sel
+        idx = np.flatnonzero(sel)
+        if len(idx):
+            raw[(start[idx] + at)[:, None] + np.arange(vals.shape[1])[None, :]] = vals[idx]
+
+    write(cap >= 6, 0, headers["node_mac"][pick])
+    write(cap >= 12, 6, headers["lxc_mac"][pick])
+    et = np.zeros(n, np.int64)
+    has_et = np.flatnonzero(cap >= 14)
+    et[has_et] = raw[start[has_et] + 12].astype(np.int64) << 8 | raw[start[has_et] + 13]
+    write((et == 0x0800) & (cap >= 30), 26, headers["ipv4"][pick])
+    write((et == 0x86DD) & (cap >= 38), 22, headers["ipv6"][pick])
+    bad = rng.random(n) < bad_share
+    what = rng.integers(0, 3, n)
+    bit = (1 << rng.integers(0, 8, n)).astype(np.uint8)
+    for w, (lo, width) in enumerate(((6, 6), (0, 6), (None, None))):
+        sel = bad & (what == w)
+        if lo is None:
+            for fam, at, wd, need in ((0x0800, 26, 4, 30), (0x86DD, 22, 16, 38)):
+                idx = np.flatnonzero(sel & (et == fam) & (cap >= need))
+                raw[start[idx] + at + rng.integers(0, wd, len(idx))] ^= bit[idx]
+        else:
+            idx = np.flatnonzero(sel & (cap >= lo + width))
+            raw[start[idx] + lo + rng.integers(0, width, len(idx))] ^= bit[idx]
+    return raw, off, wire, lxc_ids[pick]

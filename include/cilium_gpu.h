@@ -464,10 +464,10 @@ typedef struct {
   uint8_t state; /* CG_CT_STATE_* */
   uint8_t op;    /* CG_CT_OP_* */
   uint8_t loopback;
-  uint8_t pad0;
+  uint8_t pad0; /* dir: 0 ingress, 1 egress (cg_l4_frames_egress_verdicts_*) */
   uint16_t rev_nat_index;
   uint16_t pad1;
-  uint32_t pad2[2];
+  uint32_t pad2[2]; /* [0]: src_sec_id of an egress record (the header's seclabel) */
   cg_ct_key key;
   uint32_t pad3;
 } cg_ct_record;
@@ -494,6 +494,142 @@ int cg_l4_frames_ct_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, co
  * new keys did not fit under max_entries; neither key is written then. */
 int cg_ct_map_apply(uint64_t h, uint32_t ct_id, const cg_ct_record* records, size_t n, const uint32_t* pkt_len,
                     const uint32_t* src_labels, int32_t* results);
+
+/* Endpoint program headers: the compile-time constants of an endpoint's
+ * from-container program (pkg/endpoint/bpf.go:154-180 writes them into the
+ * program's header file), one 64-byte record per slot of the policy array.
+ *  - set_headers / clear_headers are all-or-nothing per call: every argument
+ *    is checked before any header changes.  Flag bits outside CG_EPH_F_* are
+ *    CG_INVALID_ARGUMENT; pad must be 0.
+ *  - A header is independent of the map in the slot: cg_policy_array_set /
+ *    clear and cg_policymap_destroy leave it alone.
+ *  - Headers are published with the array's snapshot: a verdict call sees a
+ *    concurrent set_headers entirely or not at all. */
+#define CG_EPH_F_IPV4 0x01u    /* LXC_IPV4 is defined: `ipv4` is valid */
+#define CG_EPH_F_NO_SMAC 0x02u /* DISABLE_SMAC_VERIFICATION (lib/lxc.h:31-43) */
+#define CG_EPH_F_NO_DMAC 0x04u /* DISABLE_DMAC_VERIFICATION (lib/lxc.h:76-88) */
+#define CG_EPH_F_NO_SIP 0x08u  /* DISABLE_SIP_VERIFICATION (lib/lxc.h:45-74) */
+typedef struct {
+  uint8_t lxc_mac[6], node_mac[6]; /* LXC_MAC, NODE_MAC */
+  uint32_t ipv4;                   /* LXC_IPV4, network order; valid with CG_EPH_F_IPV4 */
+  uint8_t ipv6[16];                /* LXC_IP */
+  uint8_t router_ip6[16];          /* ROUTER_IP (icmp6_handle) */
+  uint32_t seclabel;               /* SECLABEL */
+  uint32_t flags;                  /* CG_EPH_F_* */
+  uint32_t pad[2];
+} cg_endpoint_header; /* 64 bytes */
+int cg_policy_array_set_headers(uint64_t h, uint32_t arr_id, const uint16_t* lxc_ids,
+                                const cg_endpoint_header* headers, size_t n);
+int cg_policy_array_clear_headers(uint64_t h, uint32_t arr_id, const uint16_t* lxc_ids, size_t n);
+/* CG_NOT_FOUND for a slot without a header. */
+int cg_policy_array_get_header(uint64_t h, uint32_t arr_id, uint16_t lxc_id, cg_endpoint_header* out);
+
+/* L4 verdicts from raw frames, egress: the endpoint's from-container program
+ * up to its verdict — handle_ingress (bpf/bpf_lxc.c:708-742),
+ * handle_ipv4_from_lxc (:432-570), handle_ipv6 + ipv6_l3_from_lxc (:389-416,
+ * :114-266) — per frame of a blob, on the map and the header in the
+ * endpoint's slot of the policy array.  The program is the one built with
+ * CONNTRACK, LB_L3 and LB_L4 over an empty services map: lb{4,6}_lookup_service
+ * finds nothing, lb*_local and lb*_rev_nat never run, ct_state_new.rev_nat_index
+ * stays 0.  MAC rewrite, forwarding and local delivery behind the verdict are
+ * not modelled.
+ *
+ * mode: CG_L4_EGRESS [| CG_L4_IGNORE_DROP]; anything else is
+ * CG_INVALID_ARGUMENT.  lxc_ids is mandatory (the program hangs on the
+ * endpoint's own veth; no lookup names the endpoint).  Exactly one of
+ * dst_labels / ipc_id is given (both or neither: CG_INVALID_ARGUMENT).
+ * ct_id 0: no conntrack map, every packet is CT_NEW; records then must be NULL
+ * (CG_INVALID_ARGUMENT).  The blob window, backwards ranges and pkt_len are
+ * those of cg_l4_frames_verdicts_*.  One hold of the handle lock takes one
+ * snapshot of the array (headers included), the ipcache and the conntrack
+ * map; the launch holds all of them.
+ *
+ * Order per frame (codes: bpf/lib/common.h:237-264):
+ *  1. empty slot: CG_DROP_MISSED_TAIL_CALL; nothing is read, no counter moves;
+ *  2. slot without a header: CG_FRAME_NO_HEADER (the engine's own: there is no
+ *     such program);
+ *  3. frame shorter than 14 bytes: CG_DROP_INVALID (the engine's choice, as on
+ *     ingress);
+ *  4. ethertype (handle_ingress's switch, :713-737): 0x0806 →
+ *     CG_FRAME_ANSWERED (the engine's own: tail_handle_arp replies itself, no
+ *     policy runs); any other non-IP ethertype → CG_DROP_UNKNOWN_L3;
+ *  5. IPv4 (:450-466): shorter than 34 → CG_DROP_INVALID; nexthdr = protocol;
+ *     is_valid_lxc_src_mac fails (bytes 6..11 != lxc_mac) →
+ *     CG_DROP_INVALID_SMAC; else is_valid_gw_dst_mac fails (bytes 0..5 !=
+ *     node_mac) → CG_DROP_INVALID_DMAC; else is_valid_lxc_src_ipv4 fails
+ *     (saddr != ipv4, or the header has no CG_EPH_F_IPV4, lib/lxc.h:55-63) →
+ *     CG_DROP_INVALID_SIP.  A CG_EPH_F_NO_* flag skips its test.
+ *     l4_off = 14 + ihl * 4, ihl as found;
+ *  6. IPv6 (:396-415, :132-146): shorter than 54 → CG_DROP_INVALID.  If the
+ *     fixed header's nexthdr is 58 (not after extension headers): shorter than
+ *     14 + 40 + 8 → CG_DROP_INVALID; the byte at 54 being 135 →
+ *     CG_FRAME_ANSWERED; 128 with daddr == router_ip6 → CG_FRAME_ANSWERED
+ *     (icmp6_handle, lib/icmp6.h:390-412).  This comes before the MAC checks.
+ *     Then SMAC / DMAC / SIP as above (is_valid_lxc_src_ip: saddr != ipv6),
+ *     then ipv6_hdrlen with the codes of the ingress walk
+ *     (CG_DROP_INVALID_EXTHDR, CG_DROP_FRAG_NOSUPPORT, CG_DROP_INVALID);
+ *  7. lb{4,6}_extract_key → extract_l4_port (lib/lb.h:192-216): TCP / UDP load
+ *     2 bytes at l4_off + 2; on failure the reference returns skb_load_bytes's
+ *     own error (l4_load_port, lib/l4.h:62-65, passes it on and IS_ERR is
+ *     true for it), not a DROP_*: CG_FRAME_EFAULT.  ICMP / ICMPv6 pass.
+ *     Anything else is DROP_UNKNOWN_L4, which only skips the service lookup;
+ *  8. the head of ct_lookup4/6 with dir = CT_EGRESS (lib/conntrack.h:496-556,
+ *     :339-400): the tuple's flags start as TUPLE_F_IN; otherwise as on
+ *     ingress: ICMP type byte missing, TCP shorter than l4_off + 14, UDP
+ *     shorter than l4_off + 4 → CG_DROP_CT_INVALID_HDR; a protocol other than
+ *     TCP / UDP / the family's ICMP → CG_DROP_CT_UNKNOWN_PROTO; the ICMP
+ *     related / echo rules and the four port bytes into {dport, sport} as
+ *     cg_l4_frames_ct_verdicts_* state them;
+ *  9. with a conntrack map, the two lookups of ct_lookup*: the tuple as loaded
+ *     first (hit: CT_RELATED with TUPLE_F_RELATED, else CT_REPLY), then the
+ *     reversed tuple (CT_ESTABLISHED, else CT_NEW); the TCP map for nexthdr 6,
+ *     else the ANY map; the scope is the lxc id, or 0 on a global map.
+ *     Without a map every packet is CT_NEW;
+ * 10. the destination identity: dst_labels[i], or the ipcache resolution of
+ *     the header's destination address (miss or sec_label 0: CG_WORLD_ID;
+ *     with no services orig_dip is the header's daddr, :493, :180);
+ * 11. policy_can_egress (lib/policy.h:150-177) {identity, dport, nexthdr,
+ *     egress = 1}, never a fragment: is_fragment is passed false, so an IPv4
+ *     fragment is judged by the bytes where its ports would be.  As on the
+ *     ingress route the policy is evaluated on the reversed tuple's dport
+ *     whatever the state, and its counters move (the reference's call on a
+ *     REPLY / RELATED packet passes the unreversed dport; here the key and its
+ *     counters are those of the call without conntrack);
+ * 12. the outcome (:528-570, :222-266): REPLY / RELATED → 0, never a proxy
+ *     port; denied → CG_DROP_POLICY, op DELETE of the matched key if
+ *     ESTABLISHED; NEW and allowed → op CREATE and the policy's verdict (0 or
+ *     the proxy port); ESTABLISHED and allowed → the verdict.
+ *     CG_L4_IGNORE_DROP turns the denial into 0 before this.
+ *
+ * Records: cg_ct_record, with two pad fields given meaning (both 0 in every
+ * record of the ingress route): pad0 = dir (0 ingress, 1 egress), pad2[0] =
+ * src_sec_id, on egress the header's seclabel (:544, :238).  A frame that
+ * returned before step 9 gets an all-zero record.  cg_ct_map_apply on a record
+ * with dir == 1 does ct_create* as CT_EGRESS (conntrack.h:706-712):
+ * tx_packets = 1, tx_bytes = pkt_len[i], rx stays 0, src_sec_id from the
+ * record (src_labels[i] is ignored for it); the related key as for ingress.
+ *
+ * Info: cg_l4_frame_info; t.identity is the destination identity, t.flags is
+ * CG_L4_F_WALKED once the walk reached the policy (never CG_L4_F_INGRESS),
+ * t.len is set from step 3 on, family from step 5 / 6, t.proto with
+ * tuple.nexthdr, t.dport and t.identity with the policy call. */
+#define CG_L4_F_WALKED 0x08u /* egress frame info only: the walk reached the policy */
+#define CG_DROP_INVALID_SMAC (-130) /* bpf/lib/common.h:237-239 */
+#define CG_DROP_INVALID_DMAC (-131)
+#define CG_DROP_INVALID_SIP (-132)
+#define CG_FRAME_ANSWERED (-3)
+#define CG_FRAME_NO_HEADER (-4)
+#define CG_FRAME_EFAULT (-14)
+int cg_l4_frames_egress_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
+                                     const uint64_t* d_raw_off, size_t n, const uint16_t* d_lxc_ids,
+                                     const uint32_t* d_dst_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
+                                     uint32_t ct_id /* 0: none */, int32_t* d_verdicts, cg_l4_frame_info* d_info,
+                                     cg_ct_record* d_records, void* stream);
+int cg_l4_frames_egress_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                      const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids,
+                                      const uint32_t* dst_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                      uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
+                                      cg_ct_record* records);
 
 /* ======================================================================== */
 /* LPM: XDP CIDR prefilter — bpf/bpf_xdp.c:88-184,                           */
@@ -1269,6 +1405,13 @@ int cg_diag_l4_frames_ct_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, c
                                    const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
                                    uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
                                    cg_ct_record* records, uint32_t* l4_off);
+/* cg_l4_frames_egress_verdicts_* on the host: the kernel's own walk
+ * (egress_walk.h) over the host views; no device, no counters. */
+int cg_diag_l4_frames_egress_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                       const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids,
+                                       const uint32_t* dst_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                       uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
+                                       cg_ct_record* records, uint32_t* l4_off);
 /* The conntrack tables' own hash of each key (before the bucket mask), and
  * the built tables' shape: buckets and the recorded probe bound per family
  * ([0] v4, [1] v6).  For tests that build probe chains. */

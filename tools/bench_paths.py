@@ -22,7 +22,10 @@ configs, one JSON line each (bench.py covers config 5, the 10K-rule HTTP set):
 * l4_frames (opt-in, --paths l4_frames): L4 verdicts from raw Ethernet frames
   — 2^24 frames snapped to 96 B over 256 endpoints, endpoint and source
   identity resolved on the device — against the tuple route on pre-extracted
-  tuples and against host extraction + upload + that route
+  tuples and against host extraction + upload + that route; with a conntrack
+  map; and the egress program (l4_frames_egress_kernel) on an egress batch of
+  the same shape, with and without conntrack and records, as ratios to the
+  ingress kernels of the same run
 
 Inputs are resident in HBM before timing; kernels are timed with HIP events
 on their stream.  Each line carries the kernel's HBM roofline (algorithmic
@@ -360,6 +363,113 @@ def _bench_l4_frames_ct(torch, dev, stream, cl, args, arr, kw, raw, off, plen, d
                              "over_no_conntrack": sec_rec / sec_plain}}
 
 
+def _bench_l4_frames_egress(torch, dev, stream, cl, args, maps, slots, ipc, s4, s6, tports, D, n, reps, sec_in,
+                            sec_in_ct, sec_in_ct_rec):
+    """l4_frames_egress_kernel on an egress batch of the ingress line's shape:
+    the same 256 maps (config 2's mix holds egress keys) in an array whose
+    slots carry endpoint headers, the same ipcache resolving destinations,
+    frames of synth.l4_egress_frames snapped to 96 bytes, tiled to 2^24.
+    Checked against cg_diag_l4_frames_egress_eval_host over the first copy;
+    timed without conntrack and, against a global map derived as
+    _bench_l4_frames_ct derives it, with and without records.  The ratios
+    are to the ingress kernels' times of this same run."""
+    from cilium_amd import _native as N
+    from cilium_amd import synth
+    from cilium_amd.classifier import CT_KEY_DTYPE, FRAME_INFO_DTYPE
+    E = len(maps)
+    arr = cl.policy_array()
+    arr.set_many(slots, maps)
+    hdrs = np.concatenate([arr.header(mac=bytes([0x0a, 0, 0, 0, e >> 8, e & 255]), node_mac="02:00:00:00:00:01",
+                                      ipv4=bytes([10, 200, e >> 4, e & 15]), ipv6=bytes([0xfd] + [0] * 14 + [e]),
+                                      router_ip6="fd00::ffff", seclabel=256 + e) for e in range(E)])
+    arr.set_headers(slots, hdrs)
+    chunks = [synth.l4_egress_frames(D // 4, slots, hdrs, s4.view(np.uint8).reshape(-1, 4), s6, np.concatenate(tports),
+                                     seed=200 + c, min_len=64, max_len=1500, snap=96) for c in range(4)]
+    raw = np.concatenate([c[0] for c in chunks])
+    lens = np.concatenate([np.diff(c[1].astype(np.int64)) for c in chunks])
+    off = np.zeros(D + 1, np.uint64)
+    np.cumsum(lens, out=off[1:])
+    plen = np.concatenate([c[2] for c in chunks])
+    lxc = np.concatenate([c[3] for c in chunks])
+    blob = len(raw)
+    d_raw = tile_dev(torch, raw, reps, dev)
+    d_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    d_off[:D + 1].copy_(torch.from_numpy(off.view(np.int64)))
+    for r in range(1, reps):
+        d_off[r * D + 1:(r + 1) * D + 1].copy_(d_off[1:D + 1] + r * blob)
+    d_len = tile_dev(torch, plen, reps, dev).view(torch.int32)
+    d_lxc = tile_dev(torch, lxc, reps, dev).view(torch.int16)
+    d_out = torch.empty(n, dtype=torch.int32, device=dev)
+    d_info = torch.empty((D, 16), dtype=torch.uint8, device=dev)
+    kw = dict(d_lxc_ids=d_lxc, ipcache=ipc, d_pkt_len=d_len, stream=stream.cuda_stream)
+    hkw = dict(lxc_ids=lxc, ipcache=ipc, pkt_len=plen)
+    arr.frame_egress_verdicts_dev(d_raw, d_off, D, d_out, d_info=d_info, **kw)
+    stream.synchronize()
+    want, winfo, l4o = arr.frame_egress_eval_host_diag(raw, off, info=True, l4_off=True, **hkw)
+    assert np.array_equal(d_out[:D].cpu().numpy(), want), "egress frame verdicts differ from the host evaluator"
+    assert np.array_equal(d_info.cpu().numpy().view(FRAME_INFO_DTYPE).reshape(-1), winfo), "egress frame info differs"
+    del d_info
+    sec = timed(torch, stream, lambda: arr.frame_egress_verdicts_dev(d_raw, d_off, n, d_out, **kw), args.steps, 2)
+    # the conntrack table: a third of the TCP / UDP frames that reach the policy get their reply key (the tuple as
+    # loaded, TUPLE_F_IN), a third their established key (reversed, TUPLE_F_OUT); random keys fill up to 2^20
+    proto = winfo["t"]["proto"]
+    sel = np.flatnonzero((winfo["t"]["flags"] != 0) & ((proto == 6) | (proto == 17)))
+    sel = sel[sel % 3 != 2]
+    b = off[:-1].astype(np.int64)[sel]
+    fam = winfo["family"][sel]
+    keys = np.zeros(len(sel), CT_KEY_DTYPE)
+    for f, so, do, size in ((4, 26, 30, 4), (6, 22, 38, 16)):
+        m = fam == f
+        keys["saddr"][m, :size] = raw[b[m][:, None] + np.arange(so, so + size)]
+        keys["daddr"][m, :size] = raw[b[m][:, None] + np.arange(do, do + size)]
+    p = b + l4o[sel]
+    keys["dport"] = raw[p].astype(np.uint16) | raw[p + 1].astype(np.uint16) << 8
+    keys["sport"] = raw[p + 2].astype(np.uint16) | raw[p + 3].astype(np.uint16) << 8
+    keys["nexthdr"], keys["family"], keys["flags"] = proto[sel], fam, N.CG_TUPLE_F_IN
+    keys["kind"] = np.where(proto[sel] == 6, N.CG_CT_MAP_TCP, N.CG_CT_MAP_ANY)
+    est = sel % 3 == 1
+    rev = keys[est].copy()
+    rev["daddr"], rev["saddr"] = keys["saddr"][est], keys["daddr"][est]
+    rev["dport"], rev["sport"], rev["flags"] = keys["sport"][est], keys["dport"][est], N.CG_TUPLE_F_OUT
+    keys[est] = rev
+    keys = np.unique(keys)
+    target = 1 << 20
+    if len(keys) < target:
+        rng = np.random.default_rng(0xC8)
+        fill = np.zeros(target - len(keys), CT_KEY_DTYPE)
+        fill["daddr"][:, :4], fill["saddr"][:, :4] = rng.integers(0, 256, (len(fill), 4)), [172, 31, 0, 0]
+        fill["sport"], fill["nexthdr"], fill["family"] = rng.integers(0, 65536, len(fill)), 6, 4
+        fill["dport"] = np.arange(len(fill)) & 0xFFFF
+        keys = np.unique(np.concatenate([keys, fill]))
+    ct = cl.conntrack_map(max_entries=max(2 * len(keys), target), global_map=True)
+    ct.update(keys)
+    d_rec = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+    arr.frame_egress_verdicts_dev(d_raw, d_off, D, d_out, conntrack=ct, d_records=d_rec, **kw)
+    stream.synchronize()
+    cwant, _, wrec = arr.frame_egress_eval_host_diag(raw, off, info=True, conntrack=ct, **hkw)
+    assert np.array_equal(d_out[:D].cpu().numpy(), cwant), "egress conntrack verdicts differ from the host evaluator"
+    assert d_rec[:D].cpu().numpy().tobytes() == wrec.tobytes(), "egress conntrack records differ"
+    sec_rec = timed(torch, stream, lambda: arr.frame_egress_verdicts_dev(d_raw, d_off, n, d_out, conntrack=ct,
+                                                                         d_records=d_rec, **kw), args.steps, 2)
+    del d_rec
+    sec_ct = timed(torch, stream, lambda: arr.frame_egress_verdicts_dev(d_raw, d_off, n, d_out, conntrack=ct, **kw),
+                   args.steps, 2)
+    done = wrec["state"] != 0
+    ct.destroy()
+    arr.destroy()
+    return {"kernel": "l4_frames_egress_kernel", "frames": n, "distinct_frames": D, "blob_bytes_per_frame": blob / D,
+            "policy_verdict_frac": float((winfo["t"]["flags"] != 0).mean()), "allowed_frac": float((want >= 0).mean()),
+            "source_check_drop_frac": float(np.isin(want, (-130, -131, -132)).mean()),
+            "no_conntrack": {"kernel_ms": sec * 1e3, "Gframes_s": n / sec / 1e9, "over_ingress_same_run": sec / sec_in},
+            "with_conntrack": {"kernel_ms": sec_ct * 1e3, "Gframes_s": n / sec_ct / 1e9,
+                               "over_ingress_ct_same_run": sec_ct / sec_in_ct, "table_keys": int(len(keys)),
+                               "state_frac_of_looked_up": {name: float((wrec["state"][done] == s).mean()) for s, name in
+                                                           ((1, "new"), (2, "established"), (3, "reply"),
+                                                            (4, "related"))}},
+            "with_conntrack_and_records": {"kernel_ms": sec_rec * 1e3, "Gframes_s": n / sec_rec / 1e9,
+                                           "over_ingress_ct_records_same_run": sec_rec / sec_in_ct_rec}}
+
+
 def bench_l4_frames(torch, dev, stream, cl, args, threads):
     """L4 verdicts from raw frames: 256 endpoints' maps (config 2's table mix)
     behind an endpoint map, a 64K-entry ipcache, Ethernet frames snapped to 96
@@ -510,6 +620,9 @@ def bench_l4_frames(torch, dev, stream, cl, args, threads):
     stream.synchronize()
     dd_o.cpu().numpy()
     wall_f = time.perf_counter() - t0
+    del dd, dd_o, d_raw, d_off, d_len, d_out
+    eg_res = _bench_l4_frames_egress(torch, dev, stream, cl, args, maps, slots, ipc, s4, s6, tports, D, n, reps, sec,
+                                     ct_res["kernel_ms"] * 1e-3, ct_res["with_records"]["kernel_ms"] * 1e-3)
     per_frame = blob / D + 8 + 4
     return line("L4 verdicts/s from raw frames across 256 endpoints (l4_frames_kernel: header walk, endpoint map, "
                 "ipcache, policy program array)", n, sec, per_frame + 4, "l4_frames_kernel", cpu,
@@ -520,6 +633,7 @@ def bench_l4_frames(torch, dev, stream, cl, args, threads):
                  "kernel_ms": sec * 1e3, "Gframes_s": n / sec / 1e9,
                  "algorithmic_bytes_per_frame_in": per_frame,
                  "with_conntrack": ct_res,
+                 "egress": eg_res,
                  "tuple_route_ceiling": {"kernel_ms": sec_a * 1e3, "tuples": n_a, "Gtuples_s": n_a / sec_a / 1e9},
                  "from_host_data": {"frames": D, "host_extract_s": t_extract, "tuple_route_wall_s": wall_b,
                                     "frames_wall_s": wall_f, "frames_left_unparsed": int(D - len(plain))}})
