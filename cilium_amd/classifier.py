@@ -850,7 +850,11 @@ class PolicyArray:
         return out[:len(tuples)]
 
     # ------------------------------------------------ from raw frames --
-    def _frame_args(self, raw, off, lxc_ids, endpoints, src_labels, ipcache, pkt_len, ignore_drop):
+    @staticmethod
+    def _frame_mode(direction: int, ignore_drop: bool) -> int:
+        return direction | (N.CG_L4_IGNORE_DROP if ignore_drop else 0)
+
+    def _frame_args(self, direction, raw, off, lxc_ids, endpoints, src_labels, ipcache, pkt_len, ignore_drop):
         raw = np.ascontiguousarray(raw, np.uint8).reshape(-1)
         off = np.ascontiguousarray(off, np.uint64).reshape(-1)
         if len(off) < 1:
@@ -864,11 +868,25 @@ class PolicyArray:
         for a in (lxc, lab, plen):
             if a is not None and len(a) != n:
                 raise ValueError("one lxc_id / src_label / pkt_len per frame")
-        mode = N.CG_L4_INGRESS | (N.CG_L4_IGNORE_DROP if ignore_drop else 0)
         # a length-0 array still has to read as "given" to the resolver check
         keep = [np.zeros(1, a.dtype) if a is not None and not len(a) else a for a in (lxc, lab, plen)]
         return (raw, off, n, keep[0], endpoints.id if endpoints is not None else 0, keep[1],
-                ipcache.id if ipcache is not None else 0, keep[2], mode)
+                ipcache.id if ipcache is not None else 0, keep[2], self._frame_mode(direction, ignore_drop))
+
+    @staticmethod
+    def _frame_outputs(n, info, records, l4_off):
+        """The output arrays of a frames call, None where not asked for
+        (records go with info), and the function that makes the call's result
+        of them: (verdicts[, info[, records]][, l4_off]), a lone array bare."""
+        out = np.zeros(max(n, 1), np.int32)
+        fi = np.zeros(max(n, 1), FRAME_INFO_DTYPE) if info else None
+        rec = np.zeros(max(n, 1), CT_RECORD_DTYPE) if info and records else None
+        lo = np.zeros(max(n, 1), np.uint32) if l4_off else None
+
+        def result():
+            res = tuple(a[:n] for a in (out, fi, rec, lo) if a is not None)
+            return res if len(res) > 1 else res[0]
+        return out, fi, rec, lo, result
 
     def frame_verdicts(self, raw, off, *, lxc_ids=None, endpoints: Optional["EndpointMap"] = None, src_labels=None,
                        ipcache: Optional["IPCache"] = None, pkt_len=None, ignore_drop: bool = False,
@@ -883,19 +901,17 @@ class PolicyArray:
         ct_lookup4/6 read in front of the policy (cg_l4_frames_ct_verdicts_host);
         info=True then returns (verdicts, FRAME_INFO records, CT_RECORD_DTYPE
         records), the last being what ConntrackMap.apply takes."""
-        raw, off, n, lxc, ep, lab, ipc, plen, mode = self._frame_args(raw, off, lxc_ids, endpoints, src_labels,
-                                                                      ipcache, pkt_len, ignore_drop)
-        out = np.zeros(max(n, 1), np.int32)
-        fi = np.zeros(max(n, 1), FRAME_INFO_DTYPE) if info else None
+        raw, off, n, lxc, ep, lab, ipc, plen, mode = self._frame_args(N.CG_L4_INGRESS, raw, off, lxc_ids, endpoints,
+                                                                      src_labels, ipcache, pkt_len, ignore_drop)
+        out, fi, rec, _, result = self._frame_outputs(n, info, conntrack is not None, False)
         if conntrack is not None:
-            rec = np.zeros(max(n, 1), CT_RECORD_DTYPE) if info else None
             N.check(N.lib.cg_l4_frames_ct_verdicts_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep,
                                                         _p(lab), ipc, _p(plen), conntrack.id, _p(out), _p(fi),
                                                         _p(rec)))
-            return (out[:n], fi[:n], rec[:n]) if info else out[:n]
-        N.check(N.lib.cg_l4_frames_verdicts_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep, _p(lab),
-                                                 ipc, _p(plen), _p(out), _p(fi)))
-        return (out[:n], fi[:n]) if info else out[:n]
+        else:
+            N.check(N.lib.cg_l4_frames_verdicts_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep,
+                                                     _p(lab), ipc, _p(plen), _p(out), _p(fi)))
+        return result()
 
     def frame_verdicts_dev(self, d_raw, d_off, n: int, d_out, *, d_lxc_ids=None,
                            endpoints: Optional["EndpointMap"] = None, d_src_labels=None,
@@ -905,7 +921,7 @@ class PolicyArray:
         """Device buffers (u8 blob, n + 1 u64 offsets, i32 verdicts, optional
         16-byte info records; with conntrack optional 64-byte CT_RECORD_DTYPE
         records), async on `stream`."""
-        mode = N.CG_L4_INGRESS | (N.CG_L4_IGNORE_DROP if ignore_drop else 0)
+        mode = self._frame_mode(N.CG_L4_INGRESS, ignore_drop)
         if conntrack is not None:
             N.check(N.lib.cg_l4_frames_ct_verdicts_dev(
                 self.cl.h, self.id, mode, _p(d_raw), _p(d_off), n, _p(d_lxc_ids),
@@ -928,29 +944,19 @@ class PolicyArray:
         (no device, no counters).  l4_off=True appends the L4 offsets found.
         With conntrack, info=True returns the CT_RECORD_DTYPE records after
         the FRAME_INFO ones."""
-        raw, off, n, lxc, ep, lab, ipc, plen, mode = self._frame_args(raw, off, lxc_ids, endpoints, src_labels,
-                                                                      ipcache, pkt_len, ignore_drop)
-        out = np.zeros(max(n, 1), np.int32)
-        fi = np.zeros(max(n, 1), FRAME_INFO_DTYPE) if info else None
-        lo = np.zeros(max(n, 1), np.uint32) if l4_off else None
+        raw, off, n, lxc, ep, lab, ipc, plen, mode = self._frame_args(N.CG_L4_INGRESS, raw, off, lxc_ids, endpoints,
+                                                                      src_labels, ipcache, pkt_len, ignore_drop)
+        out, fi, rec, lo, result = self._frame_outputs(n, info, conntrack is not None, l4_off)
         if conntrack is not None:
-            rec = np.zeros(max(n, 1), CT_RECORD_DTYPE) if info else None
             N.check(N.lib.cg_diag_l4_frames_ct_eval_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep,
                                                          _p(lab), ipc, _p(plen), conntrack.id, _p(out), _p(fi),
                                                          _p(rec), _p(lo)))
-            res = (out[:n],) + ((fi[:n], rec[:n]) if info else ()) + ((lo[:n],) if l4_off else ())
-            return res if len(res) > 1 else res[0]
-        N.check(N.lib.cg_diag_l4_frames_eval_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep, _p(lab),
-                                                  ipc, _p(plen), _p(out), _p(fi), _p(lo)))
-        res = (out[:n],) + ((fi[:n],) if info else ()) + ((lo[:n],) if l4_off else ())
-        return res if len(res) > 1 else res[0]
+        else:
+            N.check(N.lib.cg_diag_l4_frames_eval_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc), ep,
+                                                      _p(lab), ipc, _p(plen), _p(out), _p(fi), _p(lo)))
+        return result()
 
     # --------------------------------------- from raw frames, egress --
-    def _egress_args(self, raw, off, lxc_ids, dst_labels, ipcache, pkt_len, ignore_drop):
-        raw, off, n, lxc, _, lab, ipc, plen, _ = self._frame_args(raw, off, lxc_ids, None, dst_labels, ipcache,
-                                                                  pkt_len, ignore_drop)
-        return raw, off, n, lxc, lab, ipc, plen, N.CG_L4_EGRESS | (N.CG_L4_IGNORE_DROP if ignore_drop else 0)
-
     def frame_egress_verdicts(self, raw, off, *, lxc_ids, dst_labels=None, ipcache: Optional["IPCache"] = None,
                               pkt_len=None, ignore_drop: bool = False, info: bool = False,
                               conntrack: Optional["ConntrackMap"] = None):
@@ -962,28 +968,23 @@ class PolicyArray:
         one launch (cg_l4_frames_egress_verdicts_host).  Returns as
         frame_verdicts does: info=True adds the FRAME_INFO records and, with
         conntrack, the CT_RECORD_DTYPE records ConntrackMap.apply takes."""
-        raw, off, n, lxc, lab, ipc, plen, mode = self._egress_args(raw, off, lxc_ids, dst_labels, ipcache, pkt_len,
-                                                                   ignore_drop)
-        out = np.zeros(max(n, 1), np.int32)
-        fi = np.zeros(max(n, 1), FRAME_INFO_DTYPE) if info else None
-        rec = np.zeros(max(n, 1), CT_RECORD_DTYPE) if info and conntrack is not None else None
+        raw, off, n, lxc, _, lab, ipc, plen, mode = self._frame_args(N.CG_L4_EGRESS, raw, off, lxc_ids, None,
+                                                                     dst_labels, ipcache, pkt_len, ignore_drop)
+        out, fi, rec, _, result = self._frame_outputs(n, info, conntrack is not None, False)
         N.check(N.lib.cg_l4_frames_egress_verdicts_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc),
                                                         _p(lab), ipc, _p(plen),
                                                         conntrack.id if conntrack is not None else 0, _p(out),
                                                         _p(fi), _p(rec)))
-        if not info:
-            return out[:n]
-        return (out[:n], fi[:n], rec[:n]) if conntrack is not None else (out[:n], fi[:n])
+        return result()
 
     def frame_egress_verdicts_dev(self, d_raw, d_off, n: int, d_out, *, d_lxc_ids, d_dst_labels=None,
                                   ipcache: Optional["IPCache"] = None, d_pkt_len=None, ignore_drop: bool = False,
                                   d_info=None, stream=None, conntrack: Optional["ConntrackMap"] = None,
                                   d_records=None) -> None:
         """Device buffers as frame_verdicts_dev takes them, async on `stream`."""
-        mode = N.CG_L4_EGRESS | (N.CG_L4_IGNORE_DROP if ignore_drop else 0)
         N.check(N.lib.cg_l4_frames_egress_verdicts_dev(
-            self.cl.h, self.id, mode, _p(d_raw), _p(d_off), n, _p(d_lxc_ids), _p(d_dst_labels),
-            ipcache.id if ipcache is not None else 0, _p(d_pkt_len), conntrack.id if conntrack is not None else 0,
+            self.cl.h, self.id, self._frame_mode(N.CG_L4_EGRESS, ignore_drop), _p(d_raw), _p(d_off), n,
+            _p(d_lxc_ids), _p(d_dst_labels), ipcache.id if ipcache is not None else 0, _p(d_pkt_len), conntrack.id if conntrack is not None else 0,
             _p(d_out), _p(d_info), _p(d_records), stream))
 
     def frame_egress_eval_host_diag(self, raw, off, *, lxc_ids, dst_labels=None, ipcache: Optional["IPCache"] = None,
@@ -991,19 +992,14 @@ class PolicyArray:
                                     l4_off: bool = False, conntrack: Optional["ConntrackMap"] = None):
         """Diagnostics only: frame_egress_verdicts by the kernel's own walk on
         the CPU (no device, no counters).  l4_off=True appends the L4 offsets."""
-        raw, off, n, lxc, lab, ipc, plen, mode = self._egress_args(raw, off, lxc_ids, dst_labels, ipcache, pkt_len,
-                                                                   ignore_drop)
-        out = np.zeros(max(n, 1), np.int32)
-        fi = np.zeros(max(n, 1), FRAME_INFO_DTYPE) if info else None
-        rec = np.zeros(max(n, 1), CT_RECORD_DTYPE) if info and conntrack is not None else None
-        lo = np.zeros(max(n, 1), np.uint32) if l4_off else None
+        raw, off, n, lxc, _, lab, ipc, plen, mode = self._frame_args(N.CG_L4_EGRESS, raw, off, lxc_ids, None,
+                                                                     dst_labels, ipcache, pkt_len, ignore_drop)
+        out, fi, rec, lo, result = self._frame_outputs(n, info, conntrack is not None, l4_off)
         N.check(N.lib.cg_diag_l4_frames_egress_eval_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc),
                                                          _p(lab), ipc, _p(plen),
                                                          conntrack.id if conntrack is not None else 0, _p(out),
                                                          _p(fi), _p(rec), _p(lo)))
-        res = (out[:n],) + ((fi[:n],) if info else ()) + ((rec[:n],) if rec is not None else ()) + \
-            ((lo[:n],) if l4_off else ())
-        return res if len(res) > 1 else res[0]
+        return result()
 
 
 class EndpointMap:

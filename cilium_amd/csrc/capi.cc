@@ -16,7 +16,7 @@
 #include "ct_map.h"
 #include "endpoint_map.h"
 #include "engine.h"
-#include "egress_walk.h"
+#include "frame_progs.h"
 #include "frame_walk.h"
 #include "http.h"
 #include "kafka.h"
@@ -1022,17 +1022,13 @@ int cg_ct_map_apply(uint64_t h, uint32_t ct_id, const cg_ct_record* records, siz
 }
 
 // ------------------------------------------- L4 verdicts from frames ----
-// One snapshot of the policy array, the endpoint map and the ipcache, taken
-// under one hold of the handle lock; the launch holds all three.
-struct FramesView {
-  L4ArrView arr;
-  std::shared_ptr<DevTables> ep_keep, ipc_keep;
-  EpMapDev ep{};
-  IpcacheDev ipc{};
-  // the conntrack map of the cg_l4_frames_ct_* entries (has_ct), part of the same snapshot
-  bool has_ct = false;
-  std::shared_ptr<DevTables> ct_keep;
-  CtMapDev ct{};
+// What an entry of the route names beside its batch.  ep_id: 0 when lxc_ids
+// name the endpoints; ct_id: NULL without a conntrack map; egress: the
+// from-container program over the array's headers, else the ingress one.
+struct FramesReq {
+  uint32_t arr_id, ep_id, ipc_id;
+  const uint32_t* ct_id;
+  bool egress;
 };
 static void check_frames_args(uint32_t mode, const void* lxc, uint32_t ep_id, const void* labels, uint32_t ipc_id) {
   if ((mode & ~CG_L4_IGNORE_DROP) != CG_L4_INGRESS)
@@ -1041,170 +1037,6 @@ static void check_frames_args(uint32_t mode, const void* lxc, uint32_t ep_id, co
   if ((labels != nullptr) == (ipc_id != 0))
     fail(CG_INVALID_ARGUMENT, "give src_labels or an ipcache, not both or neither");
 }
-static FramesView frames_view(Engine& e, uint32_t arr_id, uint32_t ep_id, uint32_t ipc_id, const uint32_t* ct_id) {
-  std::lock_guard<std::mutex> lk(e.mu);
-  FramesView v;
-  if (ct_id) {
-    CtMapState& p = get_ct(e, *ct_id);
-    if (p.dirty) p.rebuild(e);
-    v.has_ct = true;
-    v.ct_keep = p.tab;
-    v.ct = p.dev;
-  }
-  v.arr = l4_array_view_locked(e, arr_id);
-  if (ep_id) {
-    EndpointMapState& p = get_ep(e, ep_id);
-    if (p.dirty) p.rebuild(e);
-    v.ep_keep = p.tab;
-    v.ep = p.dev;
-  }
-  if (ipc_id) {
-    IpcacheState& p = get_ipc(e, ipc_id);
-    if (p.dirty) p.rebuild(e);
-    v.ipc_keep = p.tab;
-    v.ipc = p.dev;
-  }
-  return v;
-}
-static void frames_launch(Engine& e, const FramesView& v, uint32_t mode, const uint8_t* d_raw, const uint64_t* d_off,
-                          size_t n, const uint16_t* d_lxc, const uint32_t* d_labels, const uint32_t* d_len,
-                          int32_t* d_out, void* d_info, void* d_recs, void* st) {
-  const EpMapDev* ep = v.ep_keep ? &v.ep : nullptr;
-  const IpcacheDev* ipc = v.ipc_keep ? &v.ipc : nullptr;
-  if (v.has_ct)
-    check_launch(launch_l4_frames_ct(v.arr.dev, ep, ipc, v.ct, d_raw, d_off, n, d_lxc, d_labels, d_len, d_out, d_info,
-                                     d_recs, mode, st, e.cus),
-                 "l4 frames conntrack kernel launch");
-  else
-    check_launch(launch_l4_frames(v.arr.dev, ep, ipc, d_raw, d_off, n, d_lxc, d_labels, d_len, d_out, d_info, mode, st,
-                                  e.cus),
-                 "l4 frames kernel launch");
-  fence(v.ct_keep, st);
-  v.arr.keep->own.fence.record(st);
-  fence(v.ep_keep, st);
-  fence(v.ipc_keep, st);
-}
-
-// ct_id: NULL for the entries without conntrack, which launch l4_frames_kernel as before.
-static void frames_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw, const uint64_t* d_raw_off,
-                       size_t n, const uint16_t* d_lxc_ids, uint32_t ep_id, const uint32_t* d_src_labels,
-                       uint32_t ipc_id, const uint32_t* d_pkt_len, const uint32_t* ct_id, int32_t* d_verdicts,
-                       cg_l4_frame_info* d_info, cg_ct_record* d_recs, void* stream) {
-  auto e = get(h);
-  check_frames_args(mode, d_lxc_ids, ep_id, d_src_labels, ipc_id);
-  e->require_gpu();
-  if (!d_raw_off || (n && !d_verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
-  const FramesView v = frames_view(*e, arr_id, ep_id, ipc_id, ct_id);
-  e->set_device();
-  frames_launch(*e, v, mode, d_raw, d_raw_off, n, d_lxc_ids, d_src_labels, d_pkt_len, d_verdicts, d_info, d_recs,
-                stream_of(*e, stream));
-}
-
-int cg_l4_frames_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
-                              const uint64_t* d_raw_off, size_t n, const uint16_t* d_lxc_ids, uint32_t ep_id,
-                              const uint32_t* d_src_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
-                              int32_t* d_verdicts, cg_l4_frame_info* d_info, void* stream) {
-  return guarded([&] {
-    frames_dev(h, arr_id, mode, d_raw, d_raw_off, n, d_lxc_ids, ep_id, d_src_labels, ipc_id, d_pkt_len, nullptr,
-               d_verdicts, d_info, nullptr, stream);
-  });
-}
-
-int cg_l4_frames_ct_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
-                                 const uint64_t* d_raw_off, size_t n, const uint16_t* d_lxc_ids, uint32_t ep_id,
-                                 const uint32_t* d_src_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
-                                 uint32_t ct_id, int32_t* d_verdicts, cg_l4_frame_info* d_info,
-                                 cg_ct_record* d_records, void* stream) {
-  return guarded([&] {
-    frames_dev(h, arr_id, mode, d_raw, d_raw_off, n, d_lxc_ids, ep_id, d_src_labels, ipc_id, d_pkt_len, &ct_id,
-               d_verdicts, d_info, d_records, stream);
-  });
-}
-
-static void* stage_in(StagingSlot& sl, int i, const void* src, size_t bytes);
-
-// The host entries' staging: the blob's window [raw_off[0], raw_off[n]), the offsets and the per-frame inputs go
-// up, launch(d_raw, d_off, d_lxc, d_labels, d_len, d_out, d_info, d_recs, stream) runs, the results come back.
-using FramesLaunch = std::function<void(const uint8_t*, const uint64_t*, const uint16_t*, const uint32_t*,
-                                        const uint32_t*, int32_t*, void*, void*, void*)>;
-static void frames_staged(Engine& e, const uint8_t* raw, const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids,
-                          const uint32_t* labels, const uint32_t* pkt_len, int32_t* verdicts, cg_l4_frame_info* info,
-                          cg_ct_record* recs, const FramesLaunch& launch) {
-  const uint64_t lo = raw_off[0], bytes = raw_off[n] > lo ? raw_off[n] - lo : 0;
-  e.set_device();
-  auto lease = e.staging.acquire(e.device);
-  const auto st = (hipStream_t)lease->stream;
-  // the kernel adds the offsets to d_raw
-  const uint8_t* d_win = (const uint8_t*)stage_in(*lease, 0, raw + lo, bytes);
-  const uint8_t* d_raw = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(d_win) - lo);
-  const uint64_t* d_off = (const uint64_t*)stage_in(*lease, 1, raw_off, (n + 1) * 8);
-  const uint16_t* d_lxc = lxc_ids ? (const uint16_t*)stage_in(*lease, 2, lxc_ids, n * 2) : nullptr;
-  const uint32_t* d_lab = labels ? (const uint32_t*)stage_in(*lease, 3, labels, n * 4) : nullptr;
-  const uint32_t* d_len = pkt_len ? (const uint32_t*)stage_in(*lease, 4, pkt_len, n * 4) : nullptr;
-  int32_t* d_out = (int32_t*)lease->dev_buf(5, n * 4);
-  void* d_info = info ? lease->dev_buf(6, n * sizeof(cg_l4_frame_info)) : nullptr;
-  void* d_recs = recs ? lease->dev_buf(7, n * sizeof(cg_ct_record)) : nullptr;
-  launch(d_raw, d_off, d_lxc, d_lab, d_len, d_out, d_info, d_recs, (void*)st);
-  int32_t* h_out = (int32_t*)lease->host_buf(5, n * 4);
-  hip_check(hipMemcpyAsync(h_out, d_out, n * 4, hipMemcpyDeviceToHost, st), "D2H");
-  void* h_info = info ? lease->host_buf(6, n * sizeof(cg_l4_frame_info)) : nullptr;
-  if (info) hip_check(hipMemcpyAsync(h_info, d_info, n * sizeof(cg_l4_frame_info), hipMemcpyDeviceToHost, st), "D2H");
-  void* h_recs = recs ? lease->host_buf(7, n * sizeof(cg_ct_record)) : nullptr;
-  if (recs) hip_check(hipMemcpyAsync(h_recs, d_recs, n * sizeof(cg_ct_record), hipMemcpyDeviceToHost, st), "D2H");
-  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-  memcpy(verdicts, h_out, n * 4);
-  if (info) memcpy(info, h_info, n * sizeof(cg_l4_frame_info));
-  if (recs) memcpy(recs, h_recs, n * sizeof(cg_ct_record));
-}
-
-static void frames_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw, const uint64_t* raw_off,
-                        size_t n, const uint16_t* lxc_ids, uint32_t ep_id, const uint32_t* src_labels,
-                        uint32_t ipc_id, const uint32_t* pkt_len, const uint32_t* ct_id, int32_t* verdicts,
-                        cg_l4_frame_info* info, cg_ct_record* recs) {
-  auto e = get(h);
-  check_frames_args(mode, lxc_ids, ep_id, src_labels, ipc_id);
-  e->require_gpu();
-  if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
-  if (raw_off[n] > raw_off[0] && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
-  const FramesView v = frames_view(*e, arr_id, ep_id, ipc_id, ct_id);
-  if (!n) return;
-  frames_staged(*e, raw, raw_off, n, lxc_ids, src_labels, pkt_len, verdicts, info, recs,
-                [&](const uint8_t* d_raw, const uint64_t* d_off, const uint16_t* d_lxc, const uint32_t* d_lab,
-                    const uint32_t* d_len, int32_t* d_out, void* d_info, void* d_recs, void* st) {
-                  frames_launch(*e, v, mode, d_raw, d_off, n, d_lxc, d_lab, d_len, d_out, d_info, d_recs, st);
-                });
-}
-
-int cg_l4_frames_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
-                               const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
-                               const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
-                               int32_t* verdicts, cg_l4_frame_info* info) {
-  return guarded([&] {
-    frames_host(h, arr_id, mode, raw, raw_off, n, lxc_ids, ep_id, src_labels, ipc_id, pkt_len, nullptr, verdicts, info,
-                nullptr);
-  });
-}
-
-int cg_l4_frames_ct_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
-                                  const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
-                                  const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
-                                  uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info, cg_ct_record* records) {
-  return guarded([&] {
-    frames_host(h, arr_id, mode, raw, raw_off, n, lxc_ids, ep_id, src_labels, ipc_id, pkt_len, &ct_id, verdicts, info,
-                records);
-  });
-}
-
-// ------------------------------------- L4 verdicts from frames, egress ----
-// One snapshot of the array with its headers, the ipcache and the conntrack
-// map, taken under one hold of the handle lock; the launch holds all of them.
-struct EgressView {
-  L4ArrView arr;
-  std::shared_ptr<DevTables> hdr_keep, ipc_keep, ct_keep;
-  EpHdrDev hdr{};
-  IpcacheDev ipc{};
-  CtMapDev ct{};
-};
 static void check_egress_args(uint32_t mode, const void* lxc, const void* labels, uint32_t ipc_id, uint32_t ct_id,
                               const void* recs) {
   if ((mode & ~CG_L4_IGNORE_DROP) != CG_L4_EGRESS)
@@ -1214,50 +1046,151 @@ static void check_egress_args(uint32_t mode, const void* lxc, const void* labels
     fail(CG_INVALID_ARGUMENT, "give dst_labels or an ipcache, not both or neither");
   if (recs && !ct_id) fail(CG_INVALID_ARGUMENT, "records need a conntrack map");
 }
-static EgressView egress_view(Engine& e, uint32_t arr_id, uint32_t ipc_id, uint32_t ct_id) {
+// The checks of every entry, in their order.  gpu: the entry launches; host: raw is read here (or staged from here).
+static void check_frames(Engine& e, const FramesReq& q, const FramesBatch& b, bool gpu, bool host) {
+  if (q.egress) check_egress_args(b.mode, b.lxc, b.labels, q.ipc_id, q.ct_id ? *q.ct_id : 0, b.recs);
+  else check_frames_args(b.mode, b.lxc, q.ep_id, b.labels, q.ipc_id);
+  if (gpu) e.require_gpu();
+  if (!b.off || (b.n && !b.out)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
+  if (host && b.off[b.n] > b.off[0] && !b.raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
+}
+
+// One snapshot of the policy array and of what the request names beside it (the endpoint map or the array's
+// headers, the ipcache, the conntrack map), taken under one hold of the handle lock; the launch holds all of them.
+struct FramesView {
+  L4ArrView arr;
+  std::shared_ptr<DevTables> ep_keep, hdr_keep, ipc_keep, ct_keep;
+  EpMapDev ep{};
+  EpHdrDev hdr{};
+  IpcacheDev ipc{};
+  CtMapDev ct{};
+};
+static FramesView frames_view(Engine& e, const FramesReq& q) {
   std::lock_guard<std::mutex> lk(e.mu);
-  EgressView v;
-  if (ct_id) {
-    CtMapState& p = get_ct(e, ct_id);
+  FramesView v;
+  if (q.ct_id) {
+    CtMapState& p = get_ct(e, *q.ct_id);
     if (p.dirty) p.rebuild(e);
     v.ct_keep = p.tab;
     v.ct = p.dev;
   }
-  v.arr = l4_array_view_locked(e, arr_id);
-  PolicyArrayState& a = get_arr(e, arr_id);
-  if (a.headers_changed || !a.hdr_tab) {
-    std::vector<uint32_t> idx;
-    std::vector<uint4> recs;
-    a.header_tables(&idx, &recs);
-    e.set_device();
-    auto t = std::make_shared<DevTables>();
-    EpHdrDev d{};
-    d.idx = t->add(idx);
-    d.recs = t->add(recs);
-    a.hdr_tab = std::move(t);  // publish
-    a.hdr_dev = d;
-    a.headers_changed = false;
+  v.arr = l4_array_view_locked(e, q.arr_id);
+  if (q.ep_id) {
+    EndpointMapState& p = get_ep(e, q.ep_id);
+    if (p.dirty) p.rebuild(e);
+    v.ep_keep = p.tab;
+    v.ep = p.dev;
   }
-  v.hdr_keep = a.hdr_tab;
-  v.hdr = a.hdr_dev;
-  if (ipc_id) {
-    IpcacheState& p = get_ipc(e, ipc_id);
+  if (q.egress) {
+    PolicyArrayState& a = get_arr(e, q.arr_id);
+    if (a.headers_changed || !a.hdr_tab) {
+      std::vector<uint32_t> idx;
+      std::vector<uint4> recs;
+      a.header_tables(&idx, &recs);
+      e.set_device();
+      auto t = std::make_shared<DevTables>();
+      EpHdrDev d{};
+      d.idx = t->add(idx);
+      d.recs = t->add(recs);
+      a.hdr_tab = std::move(t);  // publish
+      a.hdr_dev = d;
+      a.headers_changed = false;
+    }
+    v.hdr_keep = a.hdr_tab;
+    v.hdr = a.hdr_dev;
+  }
+  if (q.ipc_id) {
+    IpcacheState& p = get_ipc(e, q.ipc_id);
     if (p.dirty) p.rebuild(e);
     v.ipc_keep = p.tab;
     v.ipc = p.dev;
   }
   return v;
 }
-static void egress_launch(Engine& e, const EgressView& v, uint32_t mode, const uint8_t* d_raw, const uint64_t* d_off,
-                          size_t n, const uint16_t* d_lxc, const uint32_t* d_labels, const uint32_t* d_len,
-                          int32_t* d_out, void* d_info, void* d_recs, void* st) {
-  check_launch(launch_l4_frames_egress(v.arr.dev, v.hdr, v.ipc_keep ? &v.ipc : nullptr, v.ct_keep ? &v.ct : nullptr,
-                                       d_raw, d_off, n, d_lxc, d_labels, d_len, d_out, d_info, d_recs, mode, st, e.cus),
-               "l4 frames egress kernel launch");
+// The launch over device buffers d: the from-container program when the view holds headers.
+static void frames_launch(Engine& e, const FramesView& v, const FramesBatch& d, void* st) {
+  const IpcacheDev* ipc = v.ipc_keep ? &v.ipc : nullptr;
+  const CtMapDev* ct = v.ct_keep ? &v.ct : nullptr;
+  if (v.hdr_keep)
+    check_launch(launch_l4_frames_egress(v.arr.dev, v.hdr, ipc, ct, d, st, e.cus), "l4 frames egress kernel launch");
+  else
+    check_launch(launch_l4_frames(v.arr.dev, v.ep_keep ? &v.ep : nullptr, ipc, ct, d, st, e.cus),
+                 ct ? "l4 frames conntrack kernel launch" : "l4 frames kernel launch");
   fence(v.ct_keep, st);
   v.arr.keep->own.fence.record(st);
+  fence(v.ep_keep, st);
   fence(v.hdr_keep, st);
   fence(v.ipc_keep, st);
+}
+
+static void frames_dev(uint64_t h, const FramesReq& q, const FramesBatch& d, void* stream) {
+  auto e = get(h);
+  check_frames(*e, q, d, true, false);
+  const FramesView v = frames_view(*e, q);
+  e->set_device();
+  frames_launch(*e, v, d, stream_of(*e, stream));
+}
+
+static void* stage_in(StagingSlot& sl, int i, const void* src, size_t bytes);
+
+// The host entries' staging: the blob's window [raw_off[0], raw_off[n]), the offsets and the per-frame inputs go
+// up, the launch runs over the device copies, the results come back.
+static void frames_staged(Engine& e, const FramesView& v, const FramesBatch& b) {
+  const size_t n = b.n;
+  const uint64_t lo = b.off[0], bytes = b.off[n] > lo ? b.off[n] - lo : 0;
+  e.set_device();
+  auto lease = e.staging.acquire(e.device);
+  const auto st = (hipStream_t)lease->stream;
+  FramesBatch d = b;
+  // the kernel adds the offsets to d.raw
+  const uint8_t* d_win = (const uint8_t*)stage_in(*lease, 0, b.raw + lo, bytes);
+  d.raw = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(d_win) - lo);
+  d.off = (const uint64_t*)stage_in(*lease, 1, b.off, (n + 1) * 8);
+  if (b.lxc) d.lxc = (const uint16_t*)stage_in(*lease, 2, b.lxc, n * 2);
+  if (b.labels) d.labels = (const uint32_t*)stage_in(*lease, 3, b.labels, n * 4);
+  if (b.pkt_len) d.pkt_len = (const uint32_t*)stage_in(*lease, 4, b.pkt_len, n * 4);
+  d.out = (int32_t*)lease->dev_buf(5, n * 4);
+  if (b.info) d.info = (cg_l4_frame_info*)lease->dev_buf(6, n * sizeof(cg_l4_frame_info));
+  if (b.recs) d.recs = (cg_ct_record*)lease->dev_buf(7, n * sizeof(cg_ct_record));
+  frames_launch(e, v, d, (void*)st);
+  int32_t* h_out = (int32_t*)lease->host_buf(5, n * 4);
+  hip_check(hipMemcpyAsync(h_out, d.out, n * 4, hipMemcpyDeviceToHost, st), "D2H");
+  void* h_info = b.info ? lease->host_buf(6, n * sizeof(cg_l4_frame_info)) : nullptr;
+  if (b.info) hip_check(hipMemcpyAsync(h_info, d.info, n * sizeof(cg_l4_frame_info), hipMemcpyDeviceToHost, st), "D2H");
+  void* h_recs = b.recs ? lease->host_buf(7, n * sizeof(cg_ct_record)) : nullptr;
+  if (b.recs) hip_check(hipMemcpyAsync(h_recs, d.recs, n * sizeof(cg_ct_record), hipMemcpyDeviceToHost, st), "D2H");
+  hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  memcpy(b.out, h_out, n * 4);
+  if (b.info) memcpy(b.info, h_info, n * sizeof(cg_l4_frame_info));
+  if (b.recs) memcpy(b.recs, h_recs, n * sizeof(cg_ct_record));
+}
+
+static void frames_host(uint64_t h, const FramesReq& q, const FramesBatch& b) {
+  auto e = get(h);
+  check_frames(*e, q, b, true, true);
+  const FramesView v = frames_view(*e, q);
+  if (b.n) frames_staged(*e, v, b);
+}
+
+int cg_l4_frames_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
+                              const uint64_t* d_raw_off, size_t n, const uint16_t* d_lxc_ids, uint32_t ep_id,
+                              const uint32_t* d_src_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
+                              int32_t* d_verdicts, cg_l4_frame_info* d_info, void* stream) {
+  return guarded([&] {
+    frames_dev(h, {arr_id, ep_id, ipc_id, nullptr, false},
+               {d_raw, d_raw_off, n, d_lxc_ids, d_src_labels, d_pkt_len, d_verdicts, d_info, nullptr, mode}, stream);
+  });
+}
+
+int cg_l4_frames_ct_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
+                                 const uint64_t* d_raw_off, size_t n, const uint16_t* d_lxc_ids, uint32_t ep_id,
+                                 const uint32_t* d_src_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
+                                 uint32_t ct_id, int32_t* d_verdicts, cg_l4_frame_info* d_info,
+                                 cg_ct_record* d_records, void* stream) {
+  return guarded([&] {
+    frames_dev(h, {arr_id, ep_id, ipc_id, &ct_id, false},
+               {d_raw, d_raw_off, n, d_lxc_ids, d_src_labels, d_pkt_len, d_verdicts, d_info, d_records, mode}, stream);
+  });
 }
 
 int cg_l4_frames_egress_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
@@ -1266,14 +1199,28 @@ int cg_l4_frames_egress_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode,
                                      uint32_t ct_id, int32_t* d_verdicts, cg_l4_frame_info* d_info,
                                      cg_ct_record* d_records, void* stream) {
   return guarded([&] {
-    auto e = get(h);
-    check_egress_args(mode, d_lxc_ids, d_dst_labels, ipc_id, ct_id, d_records);
-    e->require_gpu();
-    if (!d_raw_off || (n && !d_verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
-    const EgressView v = egress_view(*e, arr_id, ipc_id, ct_id);
-    e->set_device();
-    egress_launch(*e, v, mode, d_raw, d_raw_off, n, d_lxc_ids, d_dst_labels, d_pkt_len, d_verdicts, d_info, d_records,
-                  stream_of(*e, stream));
+    frames_dev(h, {arr_id, 0, ipc_id, ct_id ? &ct_id : nullptr, true},
+               {d_raw, d_raw_off, n, d_lxc_ids, d_dst_labels, d_pkt_len, d_verdicts, d_info, d_records, mode}, stream);
+  });
+}
+
+int cg_l4_frames_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                               const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
+                               const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                               int32_t* verdicts, cg_l4_frame_info* info) {
+  return guarded([&] {
+    frames_host(h, {arr_id, ep_id, ipc_id, nullptr, false},
+                {raw, raw_off, n, lxc_ids, src_labels, pkt_len, verdicts, info, nullptr, mode});
+  });
+}
+
+int cg_l4_frames_ct_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                  const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
+                                  const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                  uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info, cg_ct_record* records) {
+  return guarded([&] {
+    frames_host(h, {arr_id, ep_id, ipc_id, &ct_id, false},
+                {raw, raw_off, n, lxc_ids, src_labels, pkt_len, verdicts, info, records, mode});
   });
 }
 
@@ -1283,18 +1230,8 @@ int cg_l4_frames_egress_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode
                                       uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
                                       cg_ct_record* recs) {
   return guarded([&] {
-    auto e = get(h);
-    check_egress_args(mode, lxc_ids, dst_labels, ipc_id, ct_id, recs);
-    e->require_gpu();
-    if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
-    if (raw_off[n] > raw_off[0] && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
-    const EgressView v = egress_view(*e, arr_id, ipc_id, ct_id);
-    if (!n) return;
-    frames_staged(*e, raw, raw_off, n, lxc_ids, dst_labels, pkt_len, verdicts, info, recs,
-                  [&](const uint8_t* d_raw, const uint64_t* d_off, const uint16_t* d_lxc, const uint32_t* d_lab,
-                      const uint32_t* d_len, int32_t* d_out, void* d_info, void* d_recs, void* st) {
-                    egress_launch(*e, v, mode, d_raw, d_off, n, d_lxc, d_lab, d_len, d_out, d_info, d_recs, st);
-                  });
+    frames_host(h, {arr_id, 0, ipc_id, ct_id ? &ct_id : nullptr, true},
+                {raw, raw_off, n, lxc_ids, dst_labels, pkt_len, verdicts, info, recs, mode});
   });
 }
 
@@ -3125,145 +3062,49 @@ struct L4ArrHostView {
   L4ArrDev dev() const { return L4ArrDev{slot.data(), recs.data()}; }
 };
 
-// Per frame as l4_frames_kernel does it: frame_walk.h over the host views of
-// the array, the endpoint map and the ipcache.  No device, no counters.
-// l4_off (may be NULL): the L4 offset the walk found, 0 where it did not get
-// that far.
-// ct_id: NULL without conntrack (frame_verdict), else frame_ct_verdict over
-// that map's host tables and a record per frame.
-static void frames_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw, const uint64_t* raw_off,
-                             size_t n, const uint16_t* lxc_ids, uint32_t ep_id, const uint32_t* src_labels,
-                             uint32_t ipc_id, const uint32_t* pkt_len, const uint32_t* ct_id, int32_t* verdicts,
-                             cg_l4_frame_info* info, cg_ct_record* ct_recs, uint32_t* l4_off) {
+// Per frame as l4_frames_kernel does it: the request's program (frame_progs.h)
+// over the host views of the array, the endpoint map or the array's headers,
+// the ipcache and the conntrack map.  No device, no counters.  l4_off (may be
+// NULL): the L4 offset the walk found, 0 where it did not get that far.
+static void frames_eval_host(uint64_t h, const FramesReq& q, const FramesBatch& b, uint32_t* l4_off) {
   auto e = get(h);
-  check_frames_args(mode, lxc_ids, ep_id, src_labels, ipc_id);
-  if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
-  const uint64_t wlo = raw_off[0], whi = raw_off[n];
-  if (whi > wlo && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
+  check_frames(*e, q, b, false, true);
   std::lock_guard<std::mutex> lk(e->mu);
-  PolicyArrayState& a = get_arr(*e, arr_id);
+  PolicyArrayState& a = get_arr(*e, q.arr_id);
   const L4ArrHostView av(*e, a);
   const L4ArrDev A = av.dev();
+  std::vector<uint32_t> hidx;
+  std::vector<uint4> hrecs;
+  if (q.egress) a.header_tables(&hidx, &hrecs);
+  const EpHdrDev H{hidx.data(), hrecs.data()};
   EpMapDev E{};
   IpcacheDev ipc{};
-  if (ep_id) {
-    EndpointMapState& p = get_ep(*e, ep_id);
+  CtMapDev C{};
+  if (q.ep_id) {
+    EndpointMapState& p = get_ep(*e, q.ep_id);
     if (p.dirty) p.rebuild(*e);
     E = p.host_view();
   }
-  if (ipc_id) {
-    IpcacheState& p = get_ipc(*e, ipc_id);
+  if (q.ipc_id) {
+    IpcacheState& p = get_ipc(*e, q.ipc_id);
     if (p.dirty) p.rebuild(*e);
     ipc = p.host_view();
   }
-  CtMapDev C{};
-  if (ct_id) {
-    CtMapState& p = get_ct(*e, *ct_id);
+  if (q.ct_id) {
+    CtMapState& p = get_ct(*e, *q.ct_id);
     if (p.dirty) p.rebuild(*e);
     C = p.host_view();
   }
-  const uint8_t* lo = raw + wlo;
-  const uint8_t* hi = whi > wlo ? raw + whi : lo;
-  for (size_t i = 0; i < n; ++i) {
-    uint64_t start;
-    const uint32_t len = frame_range(raw_off[i], raw_off[i + 1], wlo, whi, &start);
-    const uint8_t* base = raw + start;
-    auto ld = [&](uint32_t o) {
-      uint32_t v = 0;
-      for (int k = 0; k < 4; ++k) {
-        const uint8_t* p = base + o + k;
-        if (p >= lo && p < hi) v |= (uint32_t)*p << (8 * k);
-      }
-      return v;
-    };
-    auto count = [](const L4Dev&, uint32_t) {};
-    const uint32_t plen = pkt_len ? pkt_len[i] : len;
-    const uint32_t lxc = lxc_ids ? lxc_ids[i] : 0u, label = src_labels ? src_labels[i] : 0u;
-    cg_l4_frame_info fi;
-    uint32_t lo4 = 0;
-    int32_t v;
-    if (ct_id) {
-      CtRecWords r;
-      if (ep_id && ipc_id)
-        v = frame_ct_verdict<true, true>(A, E, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
-      else if (ep_id)
-        v = frame_ct_verdict<true, false>(A, E, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
-      else if (ipc_id)
-        v = frame_ct_verdict<false, true>(A, E, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
-      else
-        v = frame_ct_verdict<false, false>(A, E, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
-      if (ct_recs) memcpy(&ct_recs[i], r.w, sizeof(cg_ct_record));
-    } else if (ep_id && ipc_id)
-      v = frame_verdict<true, true>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
-    else if (ep_id) v = frame_verdict<true, false>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
-    else if (ipc_id) v = frame_verdict<false, true>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
-    else v = frame_verdict<false, false>(A, E, ipc, ld, len, lxc, label, plen, mode, &fi, &lo4, count);
-    verdicts[i] = v;
-    if (info) info[i] = fi;
-    if (l4_off) l4_off[i] = lo4;
-  }
-}
-
-int cg_diag_l4_frames_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
-                                const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
-                                const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
-                                int32_t* verdicts, cg_l4_frame_info* info, uint32_t* l4_off) {
-  return guarded([&] {
-    frames_eval_host(h, arr_id, mode, raw, raw_off, n, lxc_ids, ep_id, src_labels, ipc_id, pkt_len, nullptr, verdicts,
-                     info, nullptr, l4_off);
-  });
-}
-
-int cg_diag_l4_frames_ct_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
-                                   const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
-                                   const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
-                                   uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
-                                   cg_ct_record* records, uint32_t* l4_off) {
-  return guarded([&] {
-    frames_eval_host(h, arr_id, mode, raw, raw_off, n, lxc_ids, ep_id, src_labels, ipc_id, pkt_len, &ct_id, verdicts,
-                     info, records, l4_off);
-  });
-}
-
-// Per frame as l4_frames_egress_kernel does it: egress_walk.h over the host
-// views of the array, its headers, the ipcache and the conntrack map.
-int cg_diag_l4_frames_egress_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
-                                       const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids,
-                                       const uint32_t* dst_labels, uint32_t ipc_id, const uint32_t* pkt_len,
-                                       uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
-                                       cg_ct_record* ct_recs, uint32_t* l4_off) {
-  return guarded([&] {
-    auto e = get(h);
-    check_egress_args(mode, lxc_ids, dst_labels, ipc_id, ct_id, ct_recs);
-    if (!raw_off || (n && !verdicts)) fail(CG_INVALID_ARGUMENT, "NULL raw_off/verdicts");
-    const uint64_t wlo = raw_off[0], whi = raw_off[n];
-    if (whi > wlo && !raw) fail(CG_INVALID_ARGUMENT, "NULL raw");
-    std::lock_guard<std::mutex> lk(e->mu);
-    PolicyArrayState& a = get_arr(*e, arr_id);
-    const L4ArrHostView av(*e, a);
-    const L4ArrDev A = av.dev();
-    std::vector<uint32_t> hidx;
-    std::vector<uint4> hrecs;
-    a.header_tables(&hidx, &hrecs);
-    const EpHdrDev H{hidx.data(), hrecs.data()};
-    IpcacheDev ipc{};
-    if (ipc_id) {
-      IpcacheState& p = get_ipc(*e, ipc_id);
-      if (p.dirty) p.rebuild(*e);
-      ipc = p.host_view();
-    }
-    CtMapDev C{};
-    if (ct_id) {
-      CtMapState& p = get_ct(*e, ct_id);
-      if (p.dirty) p.rebuild(*e);
-      C = p.host_view();
-    }
-    const uint8_t* lo = raw + wlo;
-    const uint8_t* hi = whi > wlo ? raw + whi : lo;
-    for (size_t i = 0; i < n; ++i) {
+  const uint64_t wlo = b.off[0], whi = b.off[b.n];
+  const uint8_t* lo = b.raw + wlo;
+  const uint8_t* hi = whi > wlo ? b.raw + whi : lo;
+  // prog: a program type's value, T: its table
+  auto loop = [&](auto prog, const auto& T) {
+    using P = decltype(prog);
+    for (size_t i = 0; i < b.n; ++i) {
       uint64_t start;
-      const uint32_t len = frame_range(raw_off[i], raw_off[i + 1], wlo, whi, &start);
-      const uint8_t* base = raw + start;
+      const uint32_t len = frame_range(b.off[i], b.off[i + 1], wlo, whi, &start);
+      const uint8_t* base = b.raw + start;
       auto ld = [&](uint32_t o) {
         uint32_t v = 0;
         for (int k = 0; k < 4; ++k) {
@@ -3273,21 +3114,53 @@ int cg_diag_l4_frames_egress_eval_host(uint64_t h, uint32_t arr_id, uint32_t mod
         return v;
       };
       auto count = [](const L4Dev&, uint32_t) {};
-      const uint32_t plen = pkt_len ? pkt_len[i] : len;
-      const uint32_t lxc = lxc_ids[i], label = dst_labels ? dst_labels[i] : 0u;
+      const uint32_t plen = b.pkt_len ? b.pkt_len[i] : len;
+      const uint32_t lxc = b.lxc ? b.lxc[i] : 0u, label = b.labels ? b.labels[i] : 0u;
       cg_l4_frame_info fi;
       CtRecWords r;
       uint32_t lo4 = 0;
-      int32_t v;
-      if (ct_id && ipc_id) v = egress_verdict<true, true>(A, H, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
-      else if (ct_id) v = egress_verdict<false, true>(A, H, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
-      else if (ipc_id) v = egress_verdict<true, false>(A, H, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
-      else v = egress_verdict<false, false>(A, H, ipc, C, ld, len, lxc, label, plen, mode, &fi, &lo4, &r, count);
-      verdicts[i] = v;
-      if (info) info[i] = fi;
-      if (ct_recs) memcpy(&ct_recs[i], r.w, sizeof(cg_ct_record));
+      b.out[i] = P::run(A, T, ipc, C, ld, len, lxc, label, plen, b.mode, &fi, &lo4, &r, count);
+      if (b.info) b.info[i] = fi;
+      if (P::kRecs && b.recs) memcpy(&b.recs[i], r.w, sizeof(cg_ct_record));
       if (l4_off) l4_off[i] = lo4;
     }
+  };
+  if (q.egress)
+    with_bools([&](auto kIpc, auto kCt) { loop(EgressProg<kIpc, kCt>{}, H); }, q.ipc_id != 0, q.ct_id != nullptr);
+  else
+    with_bools([&](auto kEp, auto kIpc, auto kCt) { loop(IngressProg<kEp, kIpc, kCt>{}, E); }, q.ep_id != 0,
+               q.ipc_id != 0, q.ct_id != nullptr);
+}
+
+int cg_diag_l4_frames_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
+                                const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                int32_t* verdicts, cg_l4_frame_info* info, uint32_t* l4_off) {
+  return guarded([&] {
+    frames_eval_host(h, {arr_id, ep_id, ipc_id, nullptr, false},
+                     {raw, raw_off, n, lxc_ids, src_labels, pkt_len, verdicts, info, nullptr, mode}, l4_off);
+  });
+}
+
+int cg_diag_l4_frames_ct_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                   const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids, uint32_t ep_id,
+                                   const uint32_t* src_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                   uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
+                                   cg_ct_record* records, uint32_t* l4_off) {
+  return guarded([&] {
+    frames_eval_host(h, {arr_id, ep_id, ipc_id, &ct_id, false},
+                     {raw, raw_off, n, lxc_ids, src_labels, pkt_len, verdicts, info, records, mode}, l4_off);
+  });
+}
+
+int cg_diag_l4_frames_egress_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                       const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids,
+                                       const uint32_t* dst_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                       uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
+                                       cg_ct_record* ct_recs, uint32_t* l4_off) {
+  return guarded([&] {
+    frames_eval_host(h, {arr_id, 0, ipc_id, ct_id ? &ct_id : nullptr, true},
+                     {raw, raw_off, n, lxc_ids, dst_labels, pkt_len, verdicts, info, ct_recs, mode}, l4_off);
   });
 }
 

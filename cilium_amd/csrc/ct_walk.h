@@ -2,9 +2,11 @@
 // ct_lookup4 / ct_lookup6 (bpf/lib/conntrack.h:467-590, :310-437) over one
 // snapshot of the cilium_ct{4,6}_* / cilium_ct_any{4,6}_* maps, and the tail of
 // ipv4_policy / ipv6_policy that acts on its result (bpf_lxc.c:948-974,
-// :814-840).  The frames kernel (kernels_l4_frames.hip, l4_frames_ct_kernel)
-// runs it per lane and cg_diag_l4_frames_ct_eval_host per frame over
-// host_view(); the walk up to the policy verdict is frame_walk.h's, unchanged.
+// :814-840).  The frames kernel (kernels_l4_frames.hip, l4_frames_kernel<P> for
+// the programs P with conntrack) runs it per lane and the
+// cg_diag_l4_frames_*_eval_host evaluators per frame over host_view(); the walk
+// up to the policy verdict is frame_walk.h's.  The from-container program
+// (egress_walk.h) ends in the same tail, ct_tail, as CT_EGRESS.
 //
 // __ct_lookup (conntrack.h:221-285) decides its return value by the key's
 // presence alone: lifetime, the closing bits and the accounting counters are
@@ -178,28 +180,30 @@ struct CtRecWords {
   uint32_t w[16];
 };
 
-// One frame through the program with conntrack.  frame_verdict runs as it
-// does without (the policy's verdict under `mode`, its counters, *o and
-// *l4_off); a frame whose walk did not reach the policy returns that code with
-// an all-zero record.  Otherwise (bpf_lxc.c:954-976, :820-840):
+// The tail of the program behind the policy's verdict v, for a frame whose walk
+// reached the policy: the two lookups and what the program does with the state
+// (bpf_lxc.c:954-976, :820-840), in both directions:
 //   REPLY / RELATED            0, never a proxy port;
 //   policy denies, ESTABLISHED CG_DROP_POLICY, op DELETE of the matched key;
 //   policy denies, NEW         CG_DROP_POLICY;
 //   NEW and allowed            the policy's verdict, op CREATE;
 //   ESTABLISHED and allowed    the policy's verdict.
-template <bool kEp, bool kIpc, class Ld, class Count>
-CG_HDI int32_t frame_ct_verdict(const L4ArrDev& A, const EpMapDev& E, const IpcacheDev& ipc, const CtMapDev& C, Ld ld,
-                                uint32_t len, uint32_t lxc, uint32_t label, uint32_t pkt_len, uint32_t mode,
-                                cg_l4_frame_info* o, uint32_t* l4_off, CtRecWords* rec, Count count) {
-  const int32_t v = frame_verdict<kEp, kIpc>(A, E, ipc, ld, len, lxc, label, pkt_len, mode, o, l4_off, count);
+// dir: 0 (CT_INGRESS) or CG_TUPLE_F_IN (CT_EGRESS, conntrack.h:504-506,
+// :347-349); the flag's value 1 is also the record's dir byte.  The record is
+// built in a local and assigned once, so that in the kernels it stays in
+// registers whatever the caller does with *rec around the call (the six
+// instantiations with conntrack sit 1 to 3 VGPRs under their limit of 128).
+template <class Ld>
+CG_HDI int32_t ct_tail(const CtMapDev& C, Ld ld, uint32_t family, uint32_t proto, uint32_t l4_off, uint32_t lxc,
+                       uint32_t dir, int32_t v, CtRecWords* rec) {
+  CtRecWords r;
 #pragma unroll
-  for (int i = 0; i < 16; ++i) rec->w[i] = 0;
-  if (!(o->t.flags & CG_L4_F_INGRESS)) return v;  // the walk returned before ct_lookup's lookups
-  const uint32_t family = o->family, proto = o->t.proto;
-  const uint32_t scope = C.global ? 0u : o->lxc_id;
+  for (int i = 0; i < 16; ++i) r.w[i] = 0;
+  const uint32_t scope = C.global ? 0u : lxc;
   const uint32_t kind = proto == 6 ? CG_CT_MAP_TCP : CG_CT_MAP_ANY;
   uint32_t tf;
-  const uint32_t ports = ct_ports(ld, family, proto, *l4_off, &tf);
+  const uint32_t ports = ct_ports(ld, family, proto, l4_off, &tf);
+  tf |= dir;
   const uint32_t last = proto | (tf | (kind == CG_CT_MAP_ANY ? kCtKindBit : 0u)) << 8 | scope << 16;
   uint32_t state, val = 0;
   if (family == 4) {
@@ -209,10 +213,10 @@ CG_HDI int32_t frame_ct_verdict(const L4ArrDev& A, const EpMapDev& E, const Ipca
     k.w[2] = ports;
     k.w[3] = last;
     state = ct_lookup<kCt4Words, kCt4Slots>(C.t4, C.mask4, C.probes4, &k, &val);
-    rec->w[4] = k.w[0];
-    rec->w[8] = k.w[1];
-    rec->w[12] = k.w[2];
-    rec->w[13] = k.w[3];
+    r.w[4] = k.w[0];
+    r.w[8] = k.w[1];
+    r.w[12] = k.w[2];
+    r.w[13] = k.w[3];
   } else {
     CtKey<kCt6Words> k;
 #pragma unroll
@@ -224,23 +228,40 @@ CG_HDI int32_t frame_ct_verdict(const L4ArrDev& A, const EpMapDev& E, const Ipca
     k.w[9] = last;
     state = ct_lookup<kCt6Words, kCt6Slots>(C.t6, C.mask6, C.probes6, &k, &val);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) rec->w[4 + i] = k.w[i];
-    rec->w[12] = k.w[8];
-    rec->w[13] = k.w[9];
+    for (int i = 0; i < 8; ++i) r.w[4 + i] = k.w[i];
+    r.w[12] = k.w[8];
+    r.w[13] = k.w[9];
   }
   // the record's tuple carries the datapath's flags; the kind has its own byte
-  const uint32_t lastw = rec->w[13];
-  rec->w[13] = lastw & 0xFFFFu & ~(kCtKindBit << 8);
-  rec->w[14] = scope | family << 16 | kind << 24;
+  r.w[13] = r.w[13] & 0xFFFFu & ~(kCtKindBit << 8);
+  r.w[14] = scope | family << 16 | kind << 24;
   const bool reply = state == CG_CT_STATE_REPLY || state == CG_CT_STATE_RELATED;
   uint32_t op = CG_CT_OP_NONE;
   int32_t out = v;
   if (reply) out = 0;
   else if (v < 0) op = state == CG_CT_STATE_ESTABLISHED ? CG_CT_OP_DELETE : CG_CT_OP_NONE;
   else if (state == CG_CT_STATE_NEW) op = CG_CT_OP_CREATE;
-  rec->w[0] = state | op << 8 | (val >> 16) << 16;
-  rec->w[1] = val & 0xFFFF;
+  r.w[0] = state | op << 8 | (val >> 16) << 16 | dir << 24;
+  r.w[1] = val & 0xFFFF;
+  *rec = r;
   return out;
+}
+
+// One frame through the ingress program with conntrack.  frame_verdict runs as
+// it does without (the policy's verdict under `mode`, its counters, *o and
+// *l4_off); a frame whose walk did not reach the policy returns that code with
+// an all-zero record, every other goes through ct_tail as CT_INGRESS.
+template <bool kEp, bool kIpc, class Ld, class Count>
+CG_HDI int32_t frame_ct_verdict(const L4ArrDev& A, const EpMapDev& E, const IpcacheDev& ipc, const CtMapDev& C, Ld ld,
+                                uint32_t len, uint32_t lxc, uint32_t label, uint32_t pkt_len, uint32_t mode,
+                                cg_l4_frame_info* o, uint32_t* l4_off, CtRecWords* rec, Count count) {
+  const int32_t v = frame_verdict<kEp, kIpc>(A, E, ipc, ld, len, lxc, label, pkt_len, mode, o, l4_off, count);
+  if (!(o->t.flags & CG_L4_F_INGRESS)) {  // the walk returned before ct_lookup's lookups
+#pragma unroll
+    for (int i = 0; i < 16; ++i) rec->w[i] = 0;
+    return v;
+  }
+  return ct_tail(C, ld, o->family, o->t.proto, *l4_off, o->lxc_id, 0u, v, rec);
 }
 
 }  // namespace cg

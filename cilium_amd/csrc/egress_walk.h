@@ -1,7 +1,7 @@
 // egress_walk.h — the endpoint's from-container program up to its verdict:
 // handle_ingress (bpf/bpf_lxc.c:708-742), handle_ipv4_from_lxc (:432-570),
 // handle_ipv6 + ipv6_l3_from_lxc (:389-416, :114-266), for one frame.  The
-// egress frames kernel (kernels_l4_frames.hip, l4_frames_egress_kernel) runs it
+// frames kernel (kernels_l4_frames.hip, l4_frames_kernel<EgressProg>) runs it
 // per lane and cg_diag_l4_frames_egress_eval_host per frame over host_view().
 //
 // The program restated is the one built with CONNTRACK, LB_L3 and LB_L4 over an
@@ -10,9 +10,9 @@
 // of the checks is the one cilium_gpu.h states for
 // cg_l4_frames_egress_verdicts_*.  The header walk behind the source checks
 // (ipv4_hdrlen / ipv6_hdrlen, the head of ct_lookup4/6) is frame_walk.h's, the
-// lookups are ct_walk.h's, both unchanged: the head of ct_lookup* fills ports
-// the same way for both directions, only the tuple's flags start as
-// TUPLE_F_IN.
+// lookups and what follows them are ct_walk.h's ct_tail: the head of
+// ct_lookup* fills ports the same way for both directions, only the tuple's
+// flags start as TUPLE_F_IN.
 #pragma once
 
 #include "ct_walk.h"
@@ -125,50 +125,7 @@ CG_HDI int32_t egress_verdict(const L4ArrDev& A, const EpHdrDev& H, const Ipcach
   const int32_t v = l4_wrap(l4_verdict(which, val, w1 >> 24), mode);
   if (!kCt) return v;
 
-  const uint32_t proto = ft.proto;
-  const uint32_t scope = C.global ? 0u : lxc;
-  const uint32_t kind = proto == 6 ? CG_CT_MAP_TCP : CG_CT_MAP_ANY;
-  uint32_t tf;
-  const uint32_t ports = ct_ports(ld, family, proto, ft.l4_off, &tf);
-  tf |= CG_TUPLE_F_IN;  // dir == CT_EGRESS (conntrack.h:504-506, :347-349)
-  const uint32_t last = proto | (tf | (kind == CG_CT_MAP_ANY ? kCtKindBit : 0u)) << 8 | scope << 16;
-  uint32_t state, cv = 0;
-  if (family == 4) {
-    CtKey<kCt4Words> k;
-    k.w[0] = ld(kEthHlen + 16);
-    k.w[1] = ld(kEthHlen + 12);
-    k.w[2] = ports;
-    k.w[3] = last;
-    state = ct_lookup<kCt4Words, kCt4Slots>(C.t4, C.mask4, C.probes4, &k, &cv);
-    rec->w[4] = k.w[0];
-    rec->w[8] = k.w[1];
-    rec->w[12] = k.w[2];
-    rec->w[13] = k.w[3];
-  } else {
-    CtKey<kCt6Words> k;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      k.w[i] = ld(kEthHlen + 24 + 4 * i);
-      k.w[4 + i] = ld(kEthHlen + 8 + 4 * i);
-    }
-    k.w[8] = ports;
-    k.w[9] = last;
-    state = ct_lookup<kCt6Words, kCt6Slots>(C.t6, C.mask6, C.probes6, &k, &cv);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) rec->w[4 + i] = k.w[i];
-    rec->w[12] = k.w[8];
-    rec->w[13] = k.w[9];
-  }
-  rec->w[13] = rec->w[13] & 0xFFFFu & ~(kCtKindBit << 8);
-  rec->w[14] = scope | family << 16 | kind << 24;
-  const bool reply = state == CG_CT_STATE_REPLY || state == CG_CT_STATE_RELATED;
-  uint32_t op = CG_CT_OP_NONE;
-  int32_t out = v;
-  if (reply) out = 0;
-  else if (v < 0) op = state == CG_CT_STATE_ESTABLISHED ? CG_CT_OP_DELETE : CG_CT_OP_NONE;
-  else if (state == CG_CT_STATE_NEW) op = CG_CT_OP_CREATE;
-  rec->w[0] = state | op << 8 | (cv >> 16) << 16 | 1u << 24;  // dir = 1
-  rec->w[1] = cv & 0xFFFF;
+  const int32_t out = ct_tail(C, ld, family, ft.proto, ft.l4_off, lxc, CG_TUPLE_F_IN, v, rec);
   rec->w[2] = h.d.x;  // src_sec_id = SECLABEL
   return out;
 }

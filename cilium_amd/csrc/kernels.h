@@ -23,27 +23,32 @@ int launch_l4_ipcache(const L4Dev& t, const IpcacheDev& ipc, int family, const v
 // addrs[i], as launch_l4_ipcache.
 int launch_l4_array(const L4ArrDev& A, const IpcacheDev& ipc, int family, const void* addrs, const uint16_t* lxc,
                     const void* tuples, size_t n, int32_t* out, uint32_t mode, void* stream, int cus);
-// L4 verdicts from raw frames (kernels_l4_frames.hip, frame_walk.h): frame i is
-// raw[off[i] .. off[i+1]).  E: the endpoint map that names each frame's
-// endpoint by destination address, or NULL and lxc[i] names it; ipc: the
-// ipcache that resolves the source address, or NULL and labels[i] is the
-// source identity.  pkt_len and info (16-byte cg_l4_frame_info) may be NULL.
-int launch_l4_frames(const L4ArrDev& A, const EpMapDev* E, const IpcacheDev* ipc, const uint8_t* raw,
-                     const uint64_t* off, size_t n, const uint16_t* lxc, const uint32_t* labels,
-                     const uint32_t* pkt_len, int32_t* out, void* info, uint32_t mode, void* stream, int cus);
-// The same with the conntrack lookup (ct_walk.h) over C; recs (64-byte
-// cg_ct_record per frame) may be NULL.
-int launch_l4_frames_ct(const L4ArrDev& A, const EpMapDev* E, const IpcacheDev* ipc, const CtMapDev& C,
-                        const uint8_t* raw, const uint64_t* off, size_t n, const uint16_t* lxc, const uint32_t* labels,
-                        const uint32_t* pkt_len, int32_t* out, void* info, void* recs, uint32_t mode, void* stream,
-                        int cus);
+// L4 verdicts from raw frames (kernels_l4_frames.hip): frame i of a batch is
+// raw[off[i] .. off[i+1]).  A launcher takes device buffers; capi.cc carries
+// an entry's host buffers in the same struct up to the staging.
+struct FramesBatch {
+  const uint8_t* raw;
+  const uint64_t* off;
+  size_t n;
+  const uint16_t* lxc;
+  const uint32_t* labels;
+  const uint32_t* pkt_len;  // may be NULL
+  int32_t* out;
+  cg_l4_frame_info* info;  // may be NULL
+  cg_ct_record* recs;      // may be NULL; not written without a conntrack map
+  uint32_t mode;
+};
+// The ingress program per frame (frame_walk.h).  E: the endpoint map that names
+// each frame's endpoint by destination address, or NULL and lxc[i] names it;
+// ipc: the ipcache that resolves the source address, or NULL and labels[i] is
+// the source identity; C: the conntrack map of the lookup in front of the
+// policy (ct_walk.h), or NULL and the kernel without the lookup runs.
+int launch_l4_frames(const L4ArrDev& A, const EpMapDev* E, const IpcacheDev* ipc, const CtMapDev* C,
+                     const FramesBatch& b, void* stream, int cus);
 // The from-container program per frame (egress_walk.h): lxc is mandatory, H the
-// array's endpoint headers; ipc NULL: labels are the destination identities;
-// C NULL: no conntrack map (recs is then not written).
+// array's endpoint headers; ipc NULL: labels are the destination identities.
 int launch_l4_frames_egress(const L4ArrDev& A, const EpHdrDev& H, const IpcacheDev* ipc, const CtMapDev* C,
-                            const uint8_t* raw, const uint64_t* off, size_t n, const uint16_t* lxc,
-                            const uint32_t* labels, const uint32_t* pkt_len, int32_t* out, void* info, void* recs,
-                            uint32_t mode, void* stream, int cus);
+                            const FramesBatch& b, void* stream, int cus);
 int launch_lpm(const LpmDev& t, bool v4_filter, bool v6_filter, const uint32_t* v4, size_t n4,
                uint8_t* out4, const uint8_t* v6, size_t n6, uint8_t* out6, void* stream, int cus);
 // order (optional): out[order[slot]] instead of out[slot] (request order;

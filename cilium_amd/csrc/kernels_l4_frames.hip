@@ -7,19 +7,18 @@
 // with the bytes shifted out (frame starts have every alignment), the
 // endpoint map and the ipcache as its frame asks, and walks the slot's map as
 // l4_array_kernel does.  Counters go to the selected map's own array.
-// l4_frames_ct_kernel is the same lane per frame with the conntrack lookup of
-// ct_walk.h between the walk and the verdict.  l4_frames_egress_kernel runs
-// the endpoint's from-container program (egress_walk.h) the same way.
+// l4_frames_kernel<P> is that lane for every program of frame_progs.h: the
+// ingress program, the same with the conntrack lookup of ct_walk.h between the
+// walk and the verdict, and the endpoint's from-container program
+// (egress_walk.h), each in its resolver combinations: twelve kernels.
 #include <hip/hip_runtime.h>
 
 #include <map>
 #include <mutex>
 
 #include "../../include/cilium_gpu.h"
-#include "ct_walk.h"
 #include "dev_types.h"
-#include "egress_walk.h"
-#include "frame_walk.h"
+#include "frame_progs.h"
 #include "kernels.h"
 
 namespace cg {
@@ -50,15 +49,19 @@ __device__ __forceinline__ uint32_t frame_word(const uint8_t* p, const uint8_t* 
   return v;
 }
 
-template <bool kEp, bool kIpc>
-__global__ __launch_bounds__(kFrmThreads) void l4_frames_kernel(L4ArrDev A, EpMapDev E, IpcacheDev ipc,
-                                                                const uint8_t* __restrict__ raw,
-                                                                const uint64_t* __restrict__ off, size_t n,
-                                                                const uint16_t* __restrict__ lxc,
-                                                                const uint32_t* __restrict__ labels,
-                                                                const uint32_t* __restrict__ pkt_len,
-                                                                int32_t* __restrict__ out, uint4* __restrict__ info,
-                                                                uint32_t mode) {
+// P: the program a lane runs (frame_progs.h).  With the conntrack lookup a lane
+// also reads its frame's two bucket lines of the conntrack table, both
+// requested before either is tested, and a record leaves as four 16-byte
+// stores.  The from-container program reads the endpoint's 64-byte header as
+// four 16-byte loads (a batch touches few distinct headers: they sit in L2) and
+// compares the MACs as the frame's first three words.  A program without
+// conntrack ignores C and recs.
+template <class P>
+__global__ __launch_bounds__(kFrmThreads) void l4_frames_kernel(
+    L4ArrDev A, typename P::Tab T, IpcacheDev ipc, CtMapDev C, const uint8_t* __restrict__ raw,
+    const uint64_t* __restrict__ off, size_t n, const uint16_t* __restrict__ lxc, const uint32_t* __restrict__ labels,
+    const uint32_t* __restrict__ pkt_len, int32_t* __restrict__ out, uint4* __restrict__ info,
+    uint4* __restrict__ recs, uint32_t mode) {
   const uint64_t wlo = off[0], whi = off[n];
   const uint8_t* lo = raw + wlo;
   const uint8_t* hi = whi > wlo ? raw + whi : lo;
@@ -68,24 +71,30 @@ __global__ __launch_bounds__(kFrmThreads) void l4_frames_kernel(L4ArrDev A, EpMa
     const uint32_t len = frame_range(off[i], off[i + 1], wlo, whi, &start);
     const uint8_t* base = raw + start;
     const uint32_t plen = pkt_len ? __builtin_nontemporal_load(pkt_len + i) : len;
-    const uint32_t id = kEp ? 0u : (uint32_t)__builtin_nontemporal_load(lxc + i);
-    const uint32_t label = kIpc ? 0u : __builtin_nontemporal_load(labels + i);
+    const uint32_t id = P::kLxc ? (uint32_t)__builtin_nontemporal_load(lxc + i) : 0u;
+    const uint32_t label = P::kLabel ? __builtin_nontemporal_load(labels + i) : 0u;
     cg_l4_frame_info fi;
+    CtRecWords r;
     uint32_t l4_off;
-    const int32_t v = frame_verdict<kEp, kIpc>(
-        A, E, ipc, [&](uint32_t o) { return frame_word(base + o, lo, hi); }, len, id, label, plen, mode, &fi, &l4_off,
-        [&](const L4Dev& t, uint32_t entry) {
+    const int32_t v = P::run(
+        A, T, ipc, C, [&](uint32_t o) { return frame_word(base + o, lo, hi); }, len, id, label, plen, mode, &fi,
+        &l4_off, &r, [&](const L4Dev& t, uint32_t entry) {
           atomicAdd(&t.counters[2 * entry], 1ULL);
           atomicAdd(&t.counters[2 * entry + 1], (unsigned long long)plen);
         });
     __builtin_nontemporal_store(v, out + i);
     if (info) {
-      uint4 r;
-      r.x = fi.t.identity;
-      r.y = (uint32_t)fi.t.dport | (uint32_t)fi.t.proto << 16 | (uint32_t)fi.t.flags << 24;
-      r.z = fi.t.len;
-      r.w = (uint32_t)fi.lxc_id | (uint32_t)fi.family << 16;
-      info[i] = r;
+      uint4 q;
+      q.x = fi.t.identity;
+      q.y = (uint32_t)fi.t.dport | (uint32_t)fi.t.proto << 16 | (uint32_t)fi.t.flags << 24;
+      q.z = fi.t.len;
+      q.w = (uint32_t)fi.lxc_id | (uint32_t)fi.family << 16;
+      info[i] = q;
+    }
+    if (P::kRecs && recs) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        recs[4 * i + q] = make_uint4(r.w[4 * q], r.w[4 * q + 1], r.w[4 * q + 2], r.w[4 * q + 3]);
     }
   }
 }
@@ -105,189 +114,35 @@ int resident_blocks(const void* fn) {
   return it->second;
 }
 
-template <bool kEp, bool kIpc>
-int launch_t(const L4ArrDev& A, const EpMapDev& E, const IpcacheDev& ipc, const uint8_t* raw, const uint64_t* off,
-             size_t n, const uint16_t* lxc, const uint32_t* labels, const uint32_t* pkt_len, int32_t* out, void* info,
-             uint32_t mode, void* stream, int cus) {
+template <class P>
+int launch(const L4ArrDev& A, const typename P::Tab& T, const IpcacheDev* ipc, const CtMapDev* C, const FramesBatch& b,
+           void* stream, int cus) {
+  if (b.n == 0) return 0;
   // sized as l4_array_kernel: grid-stride over exactly the blocks resident at once
-  size_t need = (n + kFrmThreads - 1) / kFrmThreads;
-  const size_t cap = (size_t)cus * resident_blocks((const void*)l4_frames_kernel<kEp, kIpc>);
+  size_t need = (b.n + kFrmThreads - 1) / kFrmThreads;
+  const size_t cap = (size_t)cus * resident_blocks((const void*)l4_frames_kernel<P>);
   if (need > cap) need = cap;
-  hipLaunchKernelGGL((l4_frames_kernel<kEp, kIpc>), dim3((unsigned)need), dim3(kFrmThreads), 0, (hipStream_t)stream, A,
-                     E, ipc, raw, off, n, lxc, labels, pkt_len, out, (uint4*)info, mode);
-  return (int)hipGetLastError();
-}
-
-// l4_frames_kernel with the conntrack lookup (ct_walk.h): the same lane per
-// frame and the same loads, then the frame's two bucket lines of the conntrack
-// table, both requested before either is tested.  A record leaves as four
-// 16-byte stores.
-template <bool kEp, bool kIpc>
-__global__ __launch_bounds__(kFrmThreads) void l4_frames_ct_kernel(L4ArrDev A, EpMapDev E, IpcacheDev ipc, CtMapDev C,
-                                                                   const uint8_t* __restrict__ raw,
-                                                                   const uint64_t* __restrict__ off, size_t n,
-                                                                   const uint16_t* __restrict__ lxc,
-                                                                   const uint32_t* __restrict__ labels,
-                                                                   const uint32_t* __restrict__ pkt_len,
-                                                                   int32_t* __restrict__ out,
-                                                                   uint4* __restrict__ info, uint4* __restrict__ recs,
-                                                                   uint32_t mode) {
-  const uint64_t wlo = off[0], whi = off[n];
-  const uint8_t* lo = raw + wlo;
-  const uint8_t* hi = whi > wlo ? raw + whi : lo;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    uint64_t start;
-    const uint32_t len = frame_range(off[i], off[i + 1], wlo, whi, &start);
-    const uint8_t* base = raw + start;
-    const uint32_t plen = pkt_len ? __builtin_nontemporal_load(pkt_len + i) : len;
-    const uint32_t id = kEp ? 0u : (uint32_t)__builtin_nontemporal_load(lxc + i);
-    const uint32_t label = kIpc ? 0u : __builtin_nontemporal_load(labels + i);
-    cg_l4_frame_info fi;
-    CtRecWords r;
-    uint32_t l4_off;
-    const int32_t v = frame_ct_verdict<kEp, kIpc>(
-        A, E, ipc, C, [&](uint32_t o) { return frame_word(base + o, lo, hi); }, len, id, label, plen, mode, &fi,
-        &l4_off, &r, [&](const L4Dev& t, uint32_t entry) {
-          atomicAdd(&t.counters[2 * entry], 1ULL);
-          atomicAdd(&t.counters[2 * entry + 1], (unsigned long long)plen);
-        });
-    __builtin_nontemporal_store(v, out + i);
-    if (info) {
-      uint4 q;
-      q.x = fi.t.identity;
-      q.y = (uint32_t)fi.t.dport | (uint32_t)fi.t.proto << 16 | (uint32_t)fi.t.flags << 24;
-      q.z = fi.t.len;
-      q.w = (uint32_t)fi.lxc_id | (uint32_t)fi.family << 16;
-      info[i] = q;
-    }
-    if (recs) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        recs[4 * i + q] = make_uint4(r.w[4 * q], r.w[4 * q + 1], r.w[4 * q + 2], r.w[4 * q + 3]);
-    }
-  }
-}
-
-template <bool kEp, bool kIpc>
-int launch_ct_t(const L4ArrDev& A, const EpMapDev& E, const IpcacheDev& ipc, const CtMapDev& C, const uint8_t* raw,
-                const uint64_t* off, size_t n, const uint16_t* lxc, const uint32_t* labels, const uint32_t* pkt_len,
-                int32_t* out, void* info, void* recs, uint32_t mode, void* stream, int cus) {
-  size_t need = (n + kFrmThreads - 1) / kFrmThreads;
-  const size_t cap = (size_t)cus * resident_blocks((const void*)l4_frames_ct_kernel<kEp, kIpc>);
-  if (need > cap) need = cap;
-  hipLaunchKernelGGL((l4_frames_ct_kernel<kEp, kIpc>), dim3((unsigned)need), dim3(kFrmThreads), 0,
-                     (hipStream_t)stream, A, E, ipc, C, raw, off, n, lxc, labels, pkt_len, out, (uint4*)info,
-                     (uint4*)recs, mode);
-  return (int)hipGetLastError();
-}
-
-
-// The from-container program (egress_walk.h): the same lane per frame.  The
-// endpoint's 64-byte header comes as four 16-byte loads (a batch touches few
-// distinct headers: they sit in L2), the MACs are compared as the frame's
-// first three words.  kCt: the conntrack lookup and a record per frame.
-template <bool kIpc, bool kCt>
-__global__ __launch_bounds__(kFrmThreads) void l4_frames_egress_kernel(
-    L4ArrDev A, EpHdrDev H, IpcacheDev ipc, CtMapDev C, const uint8_t* __restrict__ raw,
-    const uint64_t* __restrict__ off, size_t n, const uint16_t* __restrict__ lxc, const uint32_t* __restrict__ labels,
-    const uint32_t* __restrict__ pkt_len, int32_t* __restrict__ out, uint4* __restrict__ info,
-    uint4* __restrict__ recs, uint32_t mode) {
-  const uint64_t wlo = off[0], whi = off[n];
-  const uint8_t* lo = raw + wlo;
-  const uint8_t* hi = whi > wlo ? raw + whi : lo;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    uint64_t start;
-    const uint32_t len = frame_range(off[i], off[i + 1], wlo, whi, &start);
-    const uint8_t* base = raw + start;
-    const uint32_t plen = pkt_len ? __builtin_nontemporal_load(pkt_len + i) : len;
-    const uint32_t id = (uint32_t)__builtin_nontemporal_load(lxc + i);
-    const uint32_t label = kIpc ? 0u : __builtin_nontemporal_load(labels + i);
-    cg_l4_frame_info fi;
-    CtRecWords r;
-    uint32_t l4_off;
-    const int32_t v = egress_verdict<kIpc, kCt>(
-        A, H, ipc, C, [&](uint32_t o) { return frame_word(base + o, lo, hi); }, len, id, label, plen, mode, &fi,
-        &l4_off, &r, [&](const L4Dev& t, uint32_t entry) {
-          atomicAdd(&t.counters[2 * entry], 1ULL);
-          atomicAdd(&t.counters[2 * entry + 1], (unsigned long long)plen);
-        });
-    __builtin_nontemporal_store(v, out + i);
-    if (info) {
-      uint4 q;
-      q.x = fi.t.identity;
-      q.y = (uint32_t)fi.t.dport | (uint32_t)fi.t.proto << 16 | (uint32_t)fi.t.flags << 24;
-      q.z = fi.t.len;
-      q.w = (uint32_t)fi.lxc_id | (uint32_t)fi.family << 16;
-      info[i] = q;
-    }
-    if (kCt && recs) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        recs[4 * i + q] = make_uint4(r.w[4 * q], r.w[4 * q + 1], r.w[4 * q + 2], r.w[4 * q + 3]);
-    }
-  }
-}
-
-template <bool kIpc, bool kCt>
-int launch_egress_t(const L4ArrDev& A, const EpHdrDev& H, const IpcacheDev& ipc, const CtMapDev& C, const uint8_t* raw,
-                    const uint64_t* off, size_t n, const uint16_t* lxc, const uint32_t* labels,
-                    const uint32_t* pkt_len, int32_t* out, void* info, void* recs, uint32_t mode, void* stream,
-                    int cus) {
-  size_t need = (n + kFrmThreads - 1) / kFrmThreads;
-  const size_t cap = (size_t)cus * resident_blocks((const void*)l4_frames_egress_kernel<kIpc, kCt>);
-  if (need > cap) need = cap;
-  hipLaunchKernelGGL((l4_frames_egress_kernel<kIpc, kCt>), dim3((unsigned)need), dim3(kFrmThreads), 0,
-                     (hipStream_t)stream, A, H, ipc, C, raw, off, n, lxc, labels, pkt_len, out, (uint4*)info,
-                     (uint4*)recs, mode);
+  hipLaunchKernelGGL((l4_frames_kernel<P>), dim3((unsigned)need), dim3(kFrmThreads), 0, (hipStream_t)stream, A, T,
+                     ipc ? *ipc : IpcacheDev{}, C ? *C : CtMapDev{}, b.raw, b.off, b.n, b.lxc, b.labels, b.pkt_len,
+                     b.out, (uint4*)b.info, (uint4*)b.recs, b.mode);
   return (int)hipGetLastError();
 }
 
 }  // namespace
 
+int launch_l4_frames(const L4ArrDev& A, const EpMapDev* E, const IpcacheDev* ipc, const CtMapDev* C,
+                     const FramesBatch& b, void* stream, int cus) {
+  return with_bools(
+      [&](auto kEp, auto kIpc, auto kCt) {
+        return launch<IngressProg<kEp, kIpc, kCt>>(A, E ? *E : EpMapDev{}, ipc, C, b, stream, cus);
+      },
+      E != nullptr, ipc != nullptr, C != nullptr);
+}
+
 int launch_l4_frames_egress(const L4ArrDev& A, const EpHdrDev& H, const IpcacheDev* ipc, const CtMapDev* C,
-                            const uint8_t* raw, const uint64_t* off, size_t n, const uint16_t* lxc,
-                            const uint32_t* labels, const uint32_t* pkt_len, int32_t* out, void* info, void* recs,
-                            uint32_t mode, void* stream, int cus) {
-  if (n == 0) return 0;
-  const IpcacheDev c = ipc ? *ipc : IpcacheDev{};
-  const CtMapDev m = C ? *C : CtMapDev{};
-  if (ipc && C)
-    return launch_egress_t<true, true>(A, H, c, m, raw, off, n, lxc, labels, pkt_len, out, info, recs, mode, stream, cus);
-  if (ipc)
-    return launch_egress_t<true, false>(A, H, c, m, raw, off, n, lxc, labels, pkt_len, out, info, recs, mode, stream, cus);
-  if (C)
-    return launch_egress_t<false, true>(A, H, c, m, raw, off, n, lxc, labels, pkt_len, out, info, recs, mode, stream, cus);
-  return launch_egress_t<false, false>(A, H, c, m, raw, off, n, lxc, labels, pkt_len, out, info, recs, mode, stream, cus);
-}
-
-int launch_l4_frames_ct(const L4ArrDev& A, const EpMapDev* E, const IpcacheDev* ipc, const CtMapDev& C,
-                        const uint8_t* raw, const uint64_t* off, size_t n, const uint16_t* lxc, const uint32_t* labels,
-                        const uint32_t* pkt_len, int32_t* out, void* info, void* recs, uint32_t mode, void* stream,
-                        int cus) {
-  if (n == 0) return 0;
-  const EpMapDev e = E ? *E : EpMapDev{};
-  const IpcacheDev c = ipc ? *ipc : IpcacheDev{};
-  if (E && ipc)
-    return launch_ct_t<true, true>(A, e, c, C, raw, off, n, lxc, labels, pkt_len, out, info, recs, mode, stream, cus);
-  if (E)
-    return launch_ct_t<true, false>(A, e, c, C, raw, off, n, lxc, labels, pkt_len, out, info, recs, mode, stream, cus);
-  if (ipc)
-    return launch_ct_t<false, true>(A, e, c, C, raw, off, n, lxc, labels, pkt_len, out, info, recs, mode, stream, cus);
-  return launch_ct_t<false, false>(A, e, c, C, raw, off, n, lxc, labels, pkt_len, out, info, recs, mode, stream, cus);
-}
-
-int launch_l4_frames(const L4ArrDev& A, const EpMapDev* E, const IpcacheDev* ipc, const uint8_t* raw,
-                     const uint64_t* off, size_t n, const uint16_t* lxc, const uint32_t* labels,
-                     const uint32_t* pkt_len, int32_t* out, void* info, uint32_t mode, void* stream, int cus) {
-  if (n == 0) return 0;
-  const EpMapDev e = E ? *E : EpMapDev{};
-  const IpcacheDev c = ipc ? *ipc : IpcacheDev{};
-  if (E && ipc) return launch_t<true, true>(A, e, c, raw, off, n, lxc, labels, pkt_len, out, info, mode, stream, cus);
-  if (E) return launch_t<true, false>(A, e, c, raw, off, n, lxc, labels, pkt_len, out, info, mode, stream, cus);
-  if (ipc) return launch_t<false, true>(A, e, c, raw, off, n, lxc, labels, pkt_len, out, info, mode, stream, cus);
-  return launch_t<false, false>(A, e, c, raw, off, n, lxc, labels, pkt_len, out, info, mode, stream, cus);
+                            const FramesBatch& b, void* stream, int cus) {
+  return with_bools([&](auto kIpc, auto kCt) { return launch<EgressProg<kIpc, kCt>>(A, H, ipc, C, b, stream, cus); },
+                    ipc != nullptr, C != nullptr);
 }
 
 }  // namespace cg

@@ -1,5 +1,5 @@
-"""l4_frames_egress_kernel against the host evaluator and the Python oracle at
-every size and resolver combination, with and without conntrack; policy
+"""l4_frames_kernel<EgressProg> against the host evaluator and the Python oracle
+at every size and resolver combination, with and without conntrack; policy
 counters against a twin array driven with the oracle's tuples through
 cg_l4_array_verdicts_* in CG_L4_EGRESS mode; the empty map, the hand-written
 cases, the round trips through the shared conntrack map, a mixed wave, header

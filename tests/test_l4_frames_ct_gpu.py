@@ -1,6 +1,7 @@
-"""l4_frames_ct_kernel against the host evaluator and the Python oracle at
-every size and resolver combination, policy counters against a twin array on
-the route without conntrack, the empty map against the existing kernel, the
+"""l4_frames_kernel<IngressProg> with conntrack against the host evaluator and
+the Python oracle at every size and resolver combination, policy counters
+against a twin array on the route without conntrack, the empty map against
+the kernel without the lookup, the
 hand-written cases, probe chains and near-miss keys on the device, a mixed
 wave, the map's snapshot and the device entry."""
 import numpy as np

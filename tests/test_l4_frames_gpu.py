@@ -1,5 +1,5 @@
-"""l4_frames_kernel against the host evaluator and against the array kernel on
-the tuples it extracted, counters entry for entry on twin maps; the
+"""l4_frames_kernel<IngressProg> against the host evaluator and against the
+array kernel on the tuples it extracted, counters entry for entry on twin maps; the
 hand-written frames; truncation checked by value; large frames; a mixed wave
 with exact counter sums; pkt_len; the endpoint map's snapshot; the device entry."""
 import numpy as np

@@ -23,7 +23,7 @@ configs, one JSON line each (bench.py covers config 5, the 10K-rule HTTP set):
   — 2^24 frames snapped to 96 B over 256 endpoints, endpoint and source
   identity resolved on the device — against the tuple route on pre-extracted
   tuples and against host extraction + upload + that route; with a conntrack
-  map; and the egress program (l4_frames_egress_kernel) on an egress batch of
+  map; and the egress program (l4_frames_kernel<EgressProg>) on an egress batch of
   the same shape, with and without conntrack and records, as ratios to the
   ingress kernels of the same run
 
@@ -295,7 +295,7 @@ def bench_l4_array(torch, dev, stream, cl, args, threads):
 
 def _bench_l4_frames_ct(torch, dev, stream, cl, args, arr, kw, raw, off, plen, d_raw, d_off, d_len, d_out, D, n,
                         sec_plain):
-    """l4_frames_ct_kernel on bench_l4_frames' batch, against a global
+    """l4_frames_kernel<IngressProg> with conntrack on bench_l4_frames' batch, against a global
     conntrack map of at least 2^20 keys derived from the frames: of the TCP /
     UDP frames whose walk completes a third get their reply key (the tuple as
     loaded), a third their established key (the reversed tuple), a third
@@ -352,7 +352,7 @@ def _bench_l4_frames_ct(torch, dev, stream, cl, args, arr, kw, raw, off, plen, d
     done = wrec["state"] != 0
     info = ct.table_info()
     ct.destroy()
-    return {"kernel": "l4_frames_ct_kernel", "table_keys": int(len(keys)),
+    return {"kernel": "l4_frames_kernel<IngressProg<ep, ipc, ct>>", "table_keys": int(len(keys)),
             "table_buckets": {"v4": info[4][0], "v6": info[6][0]}, "table_probe_bound": {"v4": info[4][1], "v6": info[6][1]},
             "table_bytes": 128 * (info[4][0] + info[6][0]),
             "state_frac_of_looked_up": {name: float((wrec["state"][done] == s).mean()) for s, name in
@@ -365,7 +365,7 @@ def _bench_l4_frames_ct(torch, dev, stream, cl, args, arr, kw, raw, off, plen, d
 
 def _bench_l4_frames_egress(torch, dev, stream, cl, args, maps, slots, ipc, s4, s6, tports, D, n, reps, sec_in,
                             sec_in_ct, sec_in_ct_rec):
-    """l4_frames_egress_kernel on an egress batch of the ingress line's shape:
+    """l4_frames_kernel<EgressProg> on an egress batch of the ingress line's shape:
     the same 256 maps (config 2's mix holds egress keys) in an array whose
     slots carry endpoint headers, the same ipcache resolving destinations,
     frames of synth.l4_egress_frames snapped to 96 bytes, tiled to 2^24.
@@ -457,7 +457,7 @@ def _bench_l4_frames_egress(torch, dev, stream, cl, args, maps, slots, ipc, s4, 
     done = wrec["state"] != 0
     ct.destroy()
     arr.destroy()
-    return {"kernel": "l4_frames_egress_kernel", "frames": n, "distinct_frames": D, "blob_bytes_per_frame": blob / D,
+    return {"kernel": "l4_frames_kernel<EgressProg>", "frames": n, "distinct_frames": D, "blob_bytes_per_frame": blob / D,
             "policy_verdict_frac": float((winfo["t"]["flags"] != 0).mean()), "allowed_frac": float((want >= 0).mean()),
             "source_check_drop_frac": float(np.isin(want, (-130, -131, -132)).mean()),
             "no_conntrack": {"kernel_ms": sec * 1e3, "Gframes_s": n / sec / 1e9, "over_ingress_same_run": sec / sec_in},
@@ -625,7 +625,7 @@ def bench_l4_frames(torch, dev, stream, cl, args, threads):
                                      ct_res["kernel_ms"] * 1e-3, ct_res["with_records"]["kernel_ms"] * 1e-3)
     per_frame = blob / D + 8 + 4
     return line("L4 verdicts/s from raw frames across 256 endpoints (l4_frames_kernel: header walk, endpoint map, "
-                "ipcache, policy program array)", n, sec, per_frame + 4, "l4_frames_kernel", cpu,
+                "ipcache, policy program array)", n, sec, per_frame + 4, "l4_frames_kernel<IngressProg<ep, ipc>>", cpu,
                 "cg_diag_l4_frames_eval_host over the first copy, one thread", 1,
                 {"config": {"workload": "256 policy maps of config 2's mix, frames snapped to 96 B", "maps": E,
                             "distinct_frames": D, "frames": n, "blob_bytes_per_frame": blob / D,
