@@ -392,6 +392,24 @@ def test_gpu_empty_ragged_and_update(gpu):
     assert np.array_equal(g4, o4) and np.array_equal(g6, o6)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [2, pytest.param(3, marks=pytest.mark.run_last), pytest.param(4, marks=pytest.mark.run_last)])
+def test_gpu_resolve_addresses_per_lane(gpu, monkeypatch, K):
+    """ipcache_kernel<K> (CILIUM_GPU_IPC_K IPv4 addresses per lane) at the
+    counts around one block's K * 256 addresses, and over many blocks."""
+    monkeypatch.setenv("CILIUM_GPU_IPC_K", str(K))
+    k, v = synth.ipcache_entries(20_000, n_nodes=64, seed=5)
+    ic = gpu.ipcache()
+    ic.update(k, v)
+    for n in (1, 255, 256 * K - 1, 256 * K, 256 * K + 1, 100_003):
+        a4, a6 = synth.ipcache_addresses(4 * n, k, seed=n)  # 70 % IPv4: at least n of each family
+        a4, a6 = a4[:n].copy(), a6[:n].copy()
+        assert len(a4) == len(a6) == n
+        g4, g6 = ic.resolve(a4, a6)
+        o4, o6 = oracle.ipcache(k, v, a4, a6)
+        assert np.array_equal(g4, o4) and np.array_equal(g6, o6), (K, n)
+
+
 # ----------------------- ipcache → L4 egress (bpf_lxc.c:509-527 v4, :205-220 v6)
 def _ipc_l4_case(n_entries: int, n: int, seed: int, family: int = 4):
     """Tuples whose flags include ingress and fragment bits: the egress flow
