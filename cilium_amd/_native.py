@@ -51,7 +51,11 @@ CG_CT_MAP_F_GLOBAL = 1
 CG_TUPLE_F_OUT, CG_TUPLE_F_IN, CG_TUPLE_F_RELATED, CG_TUPLE_F_SERVICE = 0, 1, 2, 4
 CG_CT_E_RX_CLOSING, CG_CT_E_TX_CLOSING, CG_CT_E_NAT46, CG_CT_E_LB_LOOPBACK, CG_CT_E_SEEN_NON_SYN = 1, 2, 4, 8, 16
 CG_CT_STATE_NONE, CG_CT_STATE_NEW, CG_CT_STATE_ESTABLISHED, CG_CT_STATE_REPLY, CG_CT_STATE_RELATED = 0, 1, 2, 3, 4
-CG_CT_OP_NONE, CG_CT_OP_CREATE, CG_CT_OP_DELETE = 0, 1, 2
+CG_CT_OP_NONE, CG_CT_OP_CREATE, CG_CT_OP_DELETE, CG_CT_OP_UPDATE_SLAVE = 0, 1, 2, 3
+CG_DROP_NO_SERVICE = -158
+CG_LB_MAP_MAX_ENTRIES = 65536
+CG_LB_NONE, CG_LB_MISS, CG_LB_TRANSLATED, CG_LB_NO_SERVICE = 0, 1, 2, 3
+CG_LB_F_L3, CG_LB_F_PORT, CG_LB_F_LOOPBACK, CG_LB_F_REVNAT = 1, 2, 4, 8
 CG_DROP_CT_CREATE_FAILED = -155
 CG_EPH_F_IPV4, CG_EPH_F_NO_SMAC, CG_EPH_F_NO_DMAC, CG_EPH_F_NO_SIP = 1, 2, 4, 8
 CG_L4_F_WALKED = 0x08
@@ -279,6 +283,25 @@ SIGNATURES = {
                                                     _p]),
     "cg_diag_l4_frames_egress_eval_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _p, _u32, _p, _u32, _p, _p,
                                                      _p, _p]),
+    "cg_lb_map_create": (C.c_int, [_u64, _u32, _u32, C.POINTER(_u32)]),
+    "cg_lb_map_destroy": (C.c_int, [_u64, _u32]),
+    "cg_lb_map_set_loopback": (C.c_int, [_u64, _u32, _u32]),
+    "cg_lb_map_service_update": (C.c_int, [_u64, _u32, _p, _p, _sz]),
+    "cg_lb_map_service_delete": (C.c_int, [_u64, _u32, _p, _sz]),
+    "cg_lb_map_service_lookup": (C.c_int, [_u64, _u32, _p, _p]),
+    "cg_lb_map_service_dump": (C.c_int, [_u64, _u32, _p, _p, _sz, C.POINTER(_sz)]),
+    "cg_lb_map_revnat_update": (C.c_int, [_u64, _u32, _p, _p, _sz]),
+    "cg_lb_map_revnat_delete": (C.c_int, [_u64, _u32, _p, _sz]),
+    "cg_lb_map_revnat_lookup": (C.c_int, [_u64, _u32, _p, _p]),
+    "cg_lb_map_revnat_dump": (C.c_int, [_u64, _u32, _p, _p, _sz, C.POINTER(_sz)]),
+    # h, arr, mode, raw, off, n, lxc, labels, ipc, pkt_len, ct, lb, hash, verdicts, info, records, svc_records, xlate
+    # [, stream | l4_off]
+    "cg_l4_frames_egress_svc_verdicts_dev": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _p, _u32, _p, _u32, _u32, _p,
+                                                       _p, _p, _p, _p, _p, _p]),
+    "cg_l4_frames_egress_svc_verdicts_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _p, _u32, _p, _u32, _u32,
+                                                        _p, _p, _p, _p, _p, _p]),
+    "cg_diag_l4_frames_egress_svc_eval_host": (C.c_int, [_u64, _u32, _u32, _p, _p, _sz, _p, _p, _u32, _p, _u32, _u32,
+                                                         _p, _p, _p, _p, _p, _p, _p]),
     "cg_diag_ct_hash": (C.c_int, [_p, _sz, _p]),
     "cg_diag_ct_map_info": (C.c_int, [_u64, _u32, _p, _p]),
 }

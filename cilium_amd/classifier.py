@@ -13,6 +13,10 @@ Mirrors the reference's entry points for the classification path:
   endpoint or global): ``frame_verdicts(..., conntrack=ct)`` runs ct_lookup4/6
   (bpf/lib/conntrack.h) in front of the policy, ``apply`` carries out the
   CREATE / DELETE ops it reports
+* ``ServiceMap`` — pkg/maps/lbmap (cilium_lb{4,6}_services and
+  cilium_lb{4,6}_reverse_nat, UpdateService / DeleteService with the slot cache):
+  ``frame_egress_verdicts(..., services=svc)`` runs lb{4,6}_lookup_service and
+  lb{4,6}_local (bpf/lib/lb.h) in front of conntrack and the policy
 * ``PreFilter``  — pkg/datapath/prefilter (Insert/Delete/Dump with revisions)
   + batched XDP ``check_filters`` (bpf/bpf_xdp.c:88-184)
 * ``Classifier.update_http_policy`` / ``http_verdicts`` — Envoy
@@ -34,6 +38,7 @@ from typing import Iterable, Optional, Sequence
 import numpy as np
 
 from . import _native as N
+from .lbmap import Backend, LBMapCache
 from .policy import PolicyEntry, PolicyKey, PortRuleKafka, htons
 
 L4_TUPLE_DTYPE = np.dtype([("identity", "<u4"), ("dport", "<u2"), ("proto", "u1"), ("flags", "u1"),
@@ -62,6 +67,18 @@ CT_RECORD_DTYPE = np.dtype([("state", "u1"), ("op", "u1"), ("loopback", "u1"), (
 ENDPOINT_HEADER_DTYPE = np.dtype([("lxc_mac", "u1", (6,)), ("node_mac", "u1", (6,)), ("ipv4", "u1", (4,)),
                                   ("ipv6", "u1", (16,)), ("router_ip6", "u1", (16,)), ("seclabel", "<u4"),
                                   ("flags", "<u4"), ("pad", "<u4", (2,))])
+# cg_lb_key / cg_lb_service / cg_lb_revnat_key / cg_lb_revnat: the service maps; cg_lb_xlate: the translation per frame
+LB_KEY_DTYPE = np.dtype([("address", "u1", (16,)), ("dport", "<u2"), ("slave", "<u2"), ("family", "u1"),
+                         ("pad", "u1", (3,))])
+LB_SERVICE_DTYPE = np.dtype([("target", "u1", (16,)), ("port", "<u2"), ("count", "<u2"), ("rev_nat_index", "<u2"),
+                             ("weight", "<u2")])
+LB_REVNAT_KEY_DTYPE = np.dtype([("index", "<u2"), ("family", "u1"), ("pad", "u1")])
+LB_REVNAT_DTYPE = np.dtype([("address", "u1", (16,)), ("port", "<u2"), ("pad", "<u2")])
+LB_XLATE_DTYPE = np.dtype([("status", "u1"), ("flags", "u1"), ("slave", "<u2"), ("rev_nat_index", "<u2"),
+                           ("dport", "<u2"), ("sport", "<u2"), ("family", "u1"), ("pad0", "u1"), ("pad1", "<u4"),
+                           ("daddr", "u1", (16,)), ("saddr", "u1", (16,))])
+assert LB_KEY_DTYPE.itemsize == 24 and LB_SERVICE_DTYPE.itemsize == 24 and LB_REVNAT_KEY_DTYPE.itemsize == 4
+assert LB_REVNAT_DTYPE.itemsize == 20 and LB_XLATE_DTYPE.itemsize == 48
 assert ENDPOINT_HEADER_DTYPE.itemsize == 64
 assert CT_KEY_DTYPE.itemsize == 44 and CT_ENTRY_DTYPE.itemsize == 56 and CT_RECORD_DTYPE.itemsize == 64
 assert ENDPOINT_KEY_DTYPE.itemsize == 20 and ENDPOINT_INFO_DTYPE.itemsize == 8 and FRAME_INFO_DTYPE.itemsize == 16
@@ -133,6 +150,11 @@ class Classifier:
         return ConntrackMap(self, max_entries, global_map)
 
     # ------------------------------------------------------------ LPM --
+    def service_map(self, max_entries: int = 0, ipv4_loopback="0.0.0.0") -> "ServiceMap":
+        """The services and reverse-NAT maps of both families in one object
+        (cg_lb_map_*), with the node's IPV4_LOOPBACK."""
+        return ServiceMap(self, max_entries, ipv4_loopback)
+
     def prefilter(self, dyn4: bool = False, dyn6: bool = False, fix4: bool = True, fix6: bool = True,
                   max_lpm: int = 0, max_hash: int = 0) -> "PreFilter":
         return PreFilter(self, dyn4, dyn6, fix4, fix6, max_lpm, max_hash)
@@ -874,19 +896,36 @@ class PolicyArray:
                 ipcache.id if ipcache is not None else 0, keep[2], self._frame_mode(direction, ignore_drop))
 
     @staticmethod
-    def _frame_outputs(n, info, records, l4_off):
+    def _frame_outputs(n, info, records, l4_off, services=False, xlate=False):
         """The output arrays of a frames call, None where not asked for
-        (records go with info), and the function that makes the call's result
-        of them: (verdicts[, info[, records]][, l4_off]), a lone array bare."""
+        (records go with info; with services so do the service records), and
+        the function that makes the call's result of them: (verdicts[, info[,
+        records[, svc_records]]][, xlate][, l4_off]), a lone array bare."""
         out = np.zeros(max(n, 1), np.int32)
         fi = np.zeros(max(n, 1), FRAME_INFO_DTYPE) if info else None
         rec = np.zeros(max(n, 1), CT_RECORD_DTYPE) if info and records else None
         lo = np.zeros(max(n, 1), np.uint32) if l4_off else None
+        if not services:
+            def result():
+                res = tuple(a[:n] for a in (out, fi, rec, lo) if a is not None)
+                return res if len(res) > 1 else res[0]
+            return out, fi, rec, lo, result
+        srec = np.zeros(max(n, 1), CT_RECORD_DTYPE) if rec is not None else None
+        xl = np.zeros(max(n, 1), LB_XLATE_DTYPE) if xlate else None
 
-        def result():
-            res = tuple(a[:n] for a in (out, fi, rec, lo) if a is not None)
+        def result_svc():
+            res = tuple(a[:n] for a in (out, fi, rec, srec, xl, lo) if a is not None)
             return res if len(res) > 1 else res[0]
-        return out, fi, rec, lo, result
+        return out, fi, rec, lo, srec, xl, result_svc
+
+    @staticmethod
+    def _svc_hash(hash, n):
+        if hash is None:
+            return None
+        h = np.ascontiguousarray(hash, np.uint32).reshape(-1)
+        if len(h) != n:
+            raise ValueError("one hash per frame")
+        return h if n else np.zeros(1, np.uint32)
 
     def frame_verdicts(self, raw, off, *, lxc_ids=None, endpoints: Optional["EndpointMap"] = None, src_labels=None,
                        ipcache: Optional["IPCache"] = None, pkt_len=None, ignore_drop: bool = False,
@@ -959,7 +998,8 @@ class PolicyArray:
     # --------------------------------------- from raw frames, egress --
     def frame_egress_verdicts(self, raw, off, *, lxc_ids, dst_labels=None, ipcache: Optional["IPCache"] = None,
                               pkt_len=None, ignore_drop: bool = False, info: bool = False,
-                              conntrack: Optional["ConntrackMap"] = None):
+                              conntrack: Optional["ConntrackMap"] = None, services: Optional["ServiceMap"] = None,
+                              hash=None, xlate: bool = False):
         """The from-container program's verdict per raw Ethernet frame sent by
         the endpoint in slot lxc_ids[i], which needs a header (set_header):
         source MAC / gateway MAC / source address checks, the conntrack lookup
@@ -967,38 +1007,73 @@ class PolicyArray:
         (dst_labels, or the ipcache resolution of the destination address),
         one launch (cg_l4_frames_egress_verdicts_host).  Returns as
         frame_verdicts does: info=True adds the FRAME_INFO records and, with
-        conntrack, the CT_RECORD_DTYPE records ConntrackMap.apply takes."""
+        conntrack, the CT_RECORD_DTYPE records ConntrackMap.apply takes.
+
+        services: the ServiceMap whose lb{4,6}_lookup_service / lb{4,6}_local
+        run in front of conntrack and the policy, which then see the backend
+        (cg_l4_frames_egress_svc_verdicts_host); needs conntrack and ipcache.
+        hash: a u32 per frame standing for the kernel's flow hash (None: the
+        engine's hash of the frame's CT_SERVICE key).  info=True then returns
+        (verdicts, FRAME_INFO, CT_EGRESS records, CT_SERVICE records); apply
+        the service records first.  xlate=True appends the LB_XLATE_DTYPE
+        translation records."""
         raw, off, n, lxc, _, lab, ipc, plen, mode = self._frame_args(N.CG_L4_EGRESS, raw, off, lxc_ids, None,
                                                                      dst_labels, ipcache, pkt_len, ignore_drop)
+        ct = conntrack.id if conntrack is not None else 0
+        if services is not None:
+            out, fi, rec, _, srec, xl, result = self._frame_outputs(n, info, True, False, True, xlate)
+            N.check(N.lib.cg_l4_frames_egress_svc_verdicts_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc),
+                                                                _p(lab), ipc, _p(plen), ct, services.id,
+                                                                _p(self._svc_hash(hash, n)), _p(out), _p(fi), _p(rec),
+                                                                _p(srec), _p(xl)))
+            return result()
         out, fi, rec, _, result = self._frame_outputs(n, info, conntrack is not None, False)
         N.check(N.lib.cg_l4_frames_egress_verdicts_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc),
-                                                        _p(lab), ipc, _p(plen),
-                                                        conntrack.id if conntrack is not None else 0, _p(out),
-                                                        _p(fi), _p(rec)))
+                                                        _p(lab), ipc, _p(plen), ct, _p(out), _p(fi), _p(rec)))
         return result()
 
     def frame_egress_verdicts_dev(self, d_raw, d_off, n: int, d_out, *, d_lxc_ids, d_dst_labels=None,
                                   ipcache: Optional["IPCache"] = None, d_pkt_len=None, ignore_drop: bool = False,
                                   d_info=None, stream=None, conntrack: Optional["ConntrackMap"] = None,
-                                  d_records=None) -> None:
-        """Device buffers as frame_verdicts_dev takes them, async on `stream`."""
+                                  d_records=None, services: Optional["ServiceMap"] = None, d_hash=None,
+                                  d_svc_records=None, d_xlate=None) -> None:
+        """Device buffers as frame_verdicts_dev takes them, async on `stream`;
+        with services also the optional u32 hashes, 64-byte service records
+        and 48-byte LB_XLATE_DTYPE records."""
+        mode = self._frame_mode(N.CG_L4_EGRESS, ignore_drop)
+        ipc, ct = ipcache.id if ipcache is not None else 0, conntrack.id if conntrack is not None else 0
+        if services is not None:
+            N.check(N.lib.cg_l4_frames_egress_svc_verdicts_dev(
+                self.cl.h, self.id, mode, _p(d_raw), _p(d_off), n, _p(d_lxc_ids), _p(d_dst_labels), ipc, _p(d_pkt_len),
+                ct, services.id, _p(d_hash), _p(d_out), _p(d_info), _p(d_records), _p(d_svc_records), _p(d_xlate),
+                stream))
+            return
+        if d_hash is not None or d_svc_records is not None or d_xlate is not None:
+            raise ValueError("d_hash / d_svc_records / d_xlate need a service map")
         N.check(N.lib.cg_l4_frames_egress_verdicts_dev(
-            self.cl.h, self.id, self._frame_mode(N.CG_L4_EGRESS, ignore_drop), _p(d_raw), _p(d_off), n,
-            _p(d_lxc_ids), _p(d_dst_labels), ipcache.id if ipcache is not None else 0, _p(d_pkt_len), conntrack.id if conntrack is not None else 0,
+            self.cl.h, self.id, mode, _p(d_raw), _p(d_off), n, _p(d_lxc_ids), _p(d_dst_labels), ipc, _p(d_pkt_len), ct,
             _p(d_out), _p(d_info), _p(d_records), stream))
 
     def frame_egress_eval_host_diag(self, raw, off, *, lxc_ids, dst_labels=None, ipcache: Optional["IPCache"] = None,
                                     pkt_len=None, ignore_drop: bool = False, info: bool = False,
-                                    l4_off: bool = False, conntrack: Optional["ConntrackMap"] = None):
+                                    l4_off: bool = False, conntrack: Optional["ConntrackMap"] = None,
+                                    services: Optional["ServiceMap"] = None, hash=None, xlate: bool = False):
         """Diagnostics only: frame_egress_verdicts by the kernel's own walk on
         the CPU (no device, no counters).  l4_off=True appends the L4 offsets."""
         raw, off, n, lxc, _, lab, ipc, plen, mode = self._frame_args(N.CG_L4_EGRESS, raw, off, lxc_ids, None,
                                                                      dst_labels, ipcache, pkt_len, ignore_drop)
+        ct = conntrack.id if conntrack is not None else 0
+        if services is not None:
+            out, fi, rec, lo, srec, xl, result = self._frame_outputs(n, info, True, l4_off, True, xlate)
+            N.check(N.lib.cg_diag_l4_frames_egress_svc_eval_host(self.cl.h, self.id, mode, _p(raw), _p(off), n,
+                                                                 _p(lxc), _p(lab), ipc, _p(plen), ct, services.id,
+                                                                 _p(self._svc_hash(hash, n)), _p(out), _p(fi),
+                                                                 _p(rec), _p(srec), _p(xl), _p(lo)))
+            return result()
         out, fi, rec, lo, result = self._frame_outputs(n, info, conntrack is not None, l4_off)
         N.check(N.lib.cg_diag_l4_frames_egress_eval_host(self.cl.h, self.id, mode, _p(raw), _p(off), n, _p(lxc),
-                                                         _p(lab), ipc, _p(plen),
-                                                         conntrack.id if conntrack is not None else 0, _p(out),
-                                                         _p(fi), _p(rec), _p(lo)))
+                                                         _p(lab), ipc, _p(plen), ct, _p(out), _p(fi), _p(rec),
+                                                         _p(lo)))
         return result()
 
 
@@ -1173,6 +1248,178 @@ class ConntrackMap:
 
     def destroy(self) -> None:
         N.check(N.lib.cg_ct_map_destroy(self.cl.h, self.id))
+
+
+class ServiceMap:
+    """pkg/maps/lbmap on the device: cilium_lb{4,6}_services and
+    cilium_lb{4,6}_reverse_nat in one object (cilium_gpu.h cg_lb_map_*), the
+    node's IPV4_LOOPBACK, and UpdateService / DeleteService with the slot cache
+    of bpfservice.go (cilium_amd.lbmap).  Ports in the raw ops are as the
+    datapath stores them (network order read as a u16); update_service and
+    delete_service take host-order ports, as the Go functions do."""
+
+    def __init__(self, cl: Classifier, max_entries: int = 0, ipv4_loopback="0.0.0.0"):
+        self.cl = cl
+        v = C.c_uint32()
+        N.check(N.lib.cg_lb_map_create(cl.h, max_entries, self._be32(ipv4_loopback), C.byref(v)))
+        self.id = v.value
+        self.max_entries = max_entries or N.CG_LB_MAP_MAX_ENTRIES
+        self.cache = LBMapCache()
+
+    @staticmethod
+    def _be32(addr) -> int:
+        return int.from_bytes(ipaddress.IPv4Address(addr).packed, "little")
+
+    def set_loopback(self, ipv4_loopback) -> None:
+        N.check(N.lib.cg_lb_map_set_loopback(self.cl.h, self.id, self._be32(ipv4_loopback)))
+
+    # ------------------------------------------------------- raw ops --
+    @staticmethod
+    def key(addr, dport_be: int = 0, slave: int = 0) -> np.ndarray:
+        """One LB_KEY_DTYPE key; addr a string or packed bytes."""
+        k = np.zeros(1, LB_KEY_DTYPE)
+        a = addr if isinstance(addr, (bytes, bytearray)) else ipaddress.ip_address(addr).packed
+        k["address"][0, :len(a)] = np.frombuffer(bytes(a), np.uint8)
+        k["family"], k["dport"], k["slave"] = (4 if len(a) == 4 else 6), dport_be, slave
+        return k
+
+    @staticmethod
+    def value(target=None, port_be: int = 0, count: int = 0, rev_nat_index: int = 0, weight: int = 0) -> np.ndarray:
+        v = np.zeros(1, LB_SERVICE_DTYPE)
+        if target is not None:
+            a = target if isinstance(target, (bytes, bytearray)) else ipaddress.ip_address(target).packed
+            v["target"][0, :len(a)] = np.frombuffer(bytes(a), np.uint8)
+        v["port"], v["count"], v["rev_nat_index"], v["weight"] = port_be, count, rev_nat_index, weight
+        return v
+
+    @staticmethod
+    def _cat(items, dtype) -> np.ndarray:
+        if isinstance(items, np.ndarray):
+            if items.dtype != dtype:
+                raise ValueError(f"expected {dtype}")
+            return np.ascontiguousarray(items).reshape(-1)
+        return np.concatenate(list(items)) if len(items) else np.zeros(0, dtype)
+
+    def update(self, keys, values) -> None:
+        """map_update_elem for each service entry; all or nothing (cg_lb_map_service_update)."""
+        k, v = self._cat(keys, LB_KEY_DTYPE), self._cat(values, LB_SERVICE_DTYPE)
+        if len(k) != len(v):
+            raise ValueError("one value per key")
+        N.check(N.lib.cg_lb_map_service_update(self.cl.h, self.id, _p(k) if len(k) else None,
+                                               _p(v) if len(k) else None, len(k)))
+
+    def delete(self, keys) -> None:
+        """CG_NOT_FOUND (nothing deleted) when a key is absent."""
+        k = self._cat(keys, LB_KEY_DTYPE)
+        N.check(N.lib.cg_lb_map_service_delete(self.cl.h, self.id, _p(k) if len(k) else None, len(k)))
+
+    def lookup(self, key) -> Optional[np.ndarray]:
+        k = self._cat(key, LB_KEY_DTYPE)[:1]
+        v = np.zeros(1, LB_SERVICE_DTYPE)
+        rc = N.lib.cg_lb_map_service_lookup(self.cl.h, self.id, _p(k), _p(v))
+        if rc == N.CG_NOT_FOUND:
+            return None
+        N.check(rc)
+        return v[0]
+
+    def dump(self) -> tuple[np.ndarray, np.ndarray]:
+        """(keys, values) by (family, address, dport's bytes as stored, slave)."""
+        n = C.c_size_t()
+        N.check(N.lib.cg_lb_map_service_dump(self.cl.h, self.id, None, None, 0, C.byref(n)))
+        k = np.zeros(max(n.value, 1), LB_KEY_DTYPE)
+        v = np.zeros(max(n.value, 1), LB_SERVICE_DTYPE)
+        N.check(N.lib.cg_lb_map_service_dump(self.cl.h, self.id, _p(k), _p(v), n.value, C.byref(n)))
+        return k[:n.value], v[:n.value]
+
+    @staticmethod
+    def _revnat_keys(indices, family) -> np.ndarray:
+        idx = np.atleast_1d(np.asarray(indices, np.uint16))
+        k = np.zeros(len(idx), LB_REVNAT_KEY_DTYPE)
+        k["index"], k["family"] = idx, family
+        return k
+
+    def update_revnat(self, indices, addrs, ports_be) -> None:
+        """Reverse-NAT entries index -> {address, port}; the family is the
+        addresses'; all or nothing (cg_lb_map_revnat_update)."""
+        addrs = [addrs] if isinstance(addrs, (str, bytes)) else list(addrs)
+        packed = [a if isinstance(a, bytes) else ipaddress.ip_address(a).packed for a in addrs]
+        k = self._revnat_keys(indices, 0)
+        v = np.zeros(len(k), LB_REVNAT_DTYPE)
+        for i, a in enumerate(packed):
+            k["family"][i] = 4 if len(a) == 4 else 6
+            v["address"][i, :len(a)] = np.frombuffer(a, np.uint8)
+        v["port"] = ports_be
+        N.check(N.lib.cg_lb_map_revnat_update(self.cl.h, self.id, _p(k) if len(k) else None,
+                                              _p(v) if len(k) else None, len(k)))
+
+    def delete_revnat(self, indices, family: int = 4) -> None:
+        k = self._revnat_keys(indices, family)
+        N.check(N.lib.cg_lb_map_revnat_delete(self.cl.h, self.id, _p(k) if len(k) else None, len(k)))
+
+    def lookup_revnat(self, index: int, family: int = 4) -> Optional[np.ndarray]:
+        k = self._revnat_keys([index], family)
+        v = np.zeros(1, LB_REVNAT_DTYPE)
+        rc = N.lib.cg_lb_map_revnat_lookup(self.cl.h, self.id, _p(k), _p(v))
+        if rc == N.CG_NOT_FOUND:
+            return None
+        N.check(rc)
+        return v[0]
+
+    def dump_revnat(self) -> tuple[np.ndarray, np.ndarray]:
+        """(keys, values) by (family, index)."""
+        n = C.c_size_t()
+        N.check(N.lib.cg_lb_map_revnat_dump(self.cl.h, self.id, None, None, 0, C.byref(n)))
+        k = np.zeros(max(n.value, 1), LB_REVNAT_KEY_DTYPE)
+        v = np.zeros(max(n.value, 1), LB_REVNAT_DTYPE)
+        N.check(N.lib.cg_lb_map_revnat_dump(self.cl.h, self.id, _p(k), _p(v), n.value, C.byref(n)))
+        return k[:n.value], v[:n.value]
+
+    # ------------------------------------------------- control plane --
+    @staticmethod
+    def _frontend(frontend):
+        addr, port = frontend
+        ip = ipaddress.ip_address(addr)
+        return ip, int(port), f"{ip}:{int(port)}"
+
+    def update_service(self, frontend, backends, add_rev_nat: bool, rev_nat_id: int) -> None:
+        """lbmap.UpdateService (lbmap.go:351-428).  frontend: (address, port);
+        backends: Backend records or (address, port[, weight]) tuples, which
+        get rev_nat_id as their RevNat.  The slot cache keeps every backend in
+        its slave slot and fills holes with duplicates; the slaves are written
+        first, then the reverse-NAT entry, then the master with the slot
+        count, and slaves past the count are removed last.  As in the
+        reference the steps are separate map updates: a ValueError (a slave
+        whose RevNat id is 0, lbmap.go:139; RevNat id 0 with add_rev_nat)
+        leaves the earlier ones written."""
+        ip, port, fid = self._frontend(frontend)
+        bes = [b if isinstance(b, Backend) else Backend(str(b[0]), int(b[1]), rev_nat_id, int(b[2]) if len(b) > 2 else 0)
+               for b in backends]
+        values = self.cache.prepare_update(fid, bes).backends()
+        nonzero = sum(1 for b in values if b.weight != 0)
+        master = self.lookup(self.key(ip.packed, htons(port), 0))
+        existing = int(master["count"]) if master is not None else 0
+        for i, b in enumerate(values):
+            if b.rev_nat == 0:
+                raise ValueError("invalid RevNat ID (0) in the Service Value")
+            self.update(self.key(ip.packed, htons(port), i + 1),
+                        self.value(ipaddress.ip_address(b.addr).packed, htons(b.port), 0, b.rev_nat, b.weight))
+        if add_rev_nat:
+            if rev_nat_id == 0:
+                raise ValueError("invalid RevNat ID (0)")
+            self.update_revnat([rev_nat_id], [ip.packed], [htons(port)])
+        self.update(self.key(ip.packed, htons(port), 0), self.value(None, 0, len(values), 0, nonzero))
+        for i in range(len(values) + 1, existing + 1):
+            self.delete(self.key(ip.packed, htons(port), i))
+
+    def delete_service(self, frontend) -> None:
+        """lbmap.DeleteService (lbmap.go:150-167): removes the master entry
+        and the service's slot cache; the caller removes the slaves first."""
+        ip, port, fid = self._frontend(frontend)
+        self.delete(self.key(ip.packed, htons(port), 0))
+        self.cache.delete(fid)
+
+    def destroy(self) -> None:
+        N.check(N.lib.cg_lb_map_destroy(self.cl.h, self.id))
 
 
 def parse_cidr(s: str) -> np.ndarray:

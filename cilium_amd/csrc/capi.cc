@@ -25,6 +25,7 @@
 #include "l4.h"
 #include "l4_array.h"
 #include "l4_walk.h"
+#include "lb_map.h"
 #include "ipcache.h"
 #include "lpm.h"
 #include "lpm_walk.h"
@@ -95,6 +96,12 @@ EndpointMapState& get_ep(Engine& e, uint32_t id) {
 CtMapState& get_ct(Engine& e, uint32_t id) {
   auto it = e.ctmaps.find(id);
   if (it == e.ctmaps.end()) fail(CG_NOT_FOUND, "unknown conntrack map id");
+  return *it->second;
+}
+
+LbMapState& get_lb(Engine& e, uint32_t id) {
+  auto it = e.lbmaps.find(id);
+  if (it == e.lbmaps.end()) fail(CG_NOT_FOUND, "unknown service map id");
   return *it->second;
 }
 
@@ -214,6 +221,7 @@ void cg_close(uint64_t h) {
     e->ipcaches.clear();
     e->epmaps.clear();
     e->ctmaps.clear();
+    e->lbmaps.clear();
     e->selcaches.clear();
     e->http.reset();
     e->kafka.reset();
@@ -981,7 +989,7 @@ int cg_ct_map_apply(uint64_t h, uint32_t ct_id, const cg_ct_record* records, siz
     CtMapState& p = get_ct(*e, ct_id);
     // every record is checked before any is carried out
     for (size_t i = 0; i < n; ++i) {
-      if (records[i].op > CG_CT_OP_DELETE) fail(CG_INVALID_ARGUMENT, "unknown conntrack op");
+      if (records[i].op > CG_CT_OP_UPDATE_SLAVE) fail(CG_INVALID_ARGUMENT, "unknown conntrack op");
       if (records[i].op != CG_CT_OP_NONE) make_ct_key(records[i].key, p.global);
     }
     for (size_t i = 0; i < n; ++i) {
@@ -993,31 +1001,240 @@ int cg_ct_map_apply(uint64_t h, uint32_t ct_id, const cg_ct_record* records, siz
         p.dirty |= p.entries.erase(k) != 0;
         continue;
       }
+      if (r.op == CG_CT_OP_UPDATE_SLAVE) {  // ct_update{4,6}_slave: a missing entry is left alone
+        auto it = p.entries.find(k);
+        if (it != p.entries.end()) {
+          it->second.slave = r.pad1;
+          p.dirty = true;
+        }
+        continue;
+      }
       cg_ct_key rel = r.key;  // the ICMP / ICMPv6 entry that relates errors to the flow
       rel.nexthdr = r.key.family == 4 ? 1 : 58;
       rel.sport = rel.dport = 0;
       rel.flags = r.key.flags | CG_TUPLE_F_RELATED;
       const CtMapState::Key kr = CtMapState::make_key(rel);
-      const size_t fresh = !p.entries.count(k) + (kr != k && !p.entries.count(kr));
-      if (p.entries.size() + fresh > p.max_entries) {
+      // ct_create4's second entry for a ct_state with addr (conntrack.h:725-753), dir != CT_INGRESS
+      const bool second = r.key.family == 4 && r.pad0 == 1 && r.pad2[1] != 0;
+      cg_ct_key two = r.key;
+      if (second) {
+        memcpy(two.daddr, &r.pad2[1], 4);
+        if (r.loopback) {
+          two.flags = CG_TUPLE_F_IN;
+          memcpy(two.saddr, &r.pad3, 4);
+        }
+      }
+      const CtMapState::Key k2 = CtMapState::make_key(two);
+      std::vector<CtMapState::Key> fresh;
+      for (const CtMapState::Key* c : {&k, &kr, &k2})
+        if (!p.entries.count(*c) && std::find(fresh.begin(), fresh.end(), *c) == fresh.end()) fresh.push_back(*c);
+      if (p.entries.size() + fresh.size() > p.max_entries) {
         if (results) results[i] = CG_DROP_CT_CREATE_FAILED;
         continue;
       }
       cg_ct_entry en{};
-      if (r.pad0 == 1) {  // dir == CT_EGRESS (conntrack.h:706-712): tx, and SECLABEL from the record
+      if (r.pad0 != 0) {  // dir != CT_INGRESS (conntrack.h:706-712): tx; CT_EGRESS has SECLABEL in the record
         en.tx_packets = 1;
         en.tx_bytes = pkt_len ? pkt_len[i] : 0;
-        en.src_sec_id = r.pad2[0];
+        en.src_sec_id = r.pad0 == 1 ? r.pad2[0] : 0;
       } else {
         en.rx_packets = 1;
         en.rx_bytes = pkt_len ? pkt_len[i] : 0;
         en.src_sec_id = src_labels ? src_labels[i] : 0;
       }
+      en.rev_nat_index = r.rev_nat_index;
+      en.slave = r.pad1;
+      if (r.loopback) en.flags |= CG_CT_E_LB_LOOPBACK;
       p.entries[k] = en;
+      if (second) p.entries[k2] = en;
       en.flags |= CG_CT_E_SEEN_NON_SYN;
       p.entries[kr] = en;
       p.dirty = true;
     }
+  });
+}
+
+// ------------------------------------------------------ service maps ----
+// cilium_lb{4,6}_services / cilium_lb{4,6}_reverse_nat (lb_map.h).
+static void check_lb_addr(uint8_t family, const uint8_t* addr, const char* what) {
+  if (family != 4 && family != 6) fail(CG_INVALID_ADDRESS, "service map family must be 4 or 6");
+  if (family == 4)
+    for (int i = 4; i < 16; ++i)
+      if (addr[i]) fail(CG_INVALID_ARGUMENT, what);
+}
+static LbMapState::Key make_lb_key(const cg_lb_key& k) {
+  check_lb_addr(k.family, k.address, "an IPv4 service key uses address bytes 0..3");
+  if (k.pad[0] | k.pad[1] | k.pad[2]) fail(CG_INVALID_ARGUMENT, "service key pad must be 0");
+  return LbMapState::make_key(k);
+}
+static std::pair<uint8_t, uint16_t> make_rn_key(const cg_lb_revnat_key& k) {
+  if (k.family != 4 && k.family != 6) fail(CG_INVALID_ADDRESS, "service map family must be 4 or 6");
+  if (k.pad) fail(CG_INVALID_ARGUMENT, "reverse NAT key pad must be 0");
+  return {k.family, k.index};
+}
+
+int cg_lb_map_create(uint64_t h, uint32_t max_entries, uint32_t ipv4_loopback, uint32_t* lb_id) {
+  return guarded([&] {
+    auto e = get(h);
+    if (!lb_id) fail(CG_INVALID_ARGUMENT, "lb_id is NULL");
+    std::lock_guard<std::mutex> lk(e->mu);
+    auto p = std::make_unique<LbMapState>();
+    if (max_entries) p->max_entries = max_entries;
+    p->loopback = ipv4_loopback;
+    const uint32_t id = e->next_id++;
+    e->lbmaps[id] = std::move(p);
+    *lb_id = id;
+  });
+}
+
+int cg_lb_map_destroy(uint64_t h, uint32_t lb_id) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    get_lb(*e, lb_id);
+    if (e->has_gpu()) dev_sync(*e, nullptr);
+    e->lbmaps.erase(lb_id);
+  });
+}
+
+int cg_lb_map_set_loopback(uint64_t h, uint32_t lb_id, uint32_t ipv4_loopback) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    LbMapState& p = get_lb(*e, lb_id);
+    p.loopback = ipv4_loopback;
+    p.dirty = true;
+  });
+}
+
+int cg_lb_map_service_update(uint64_t h, uint32_t lb_id, const cg_lb_key* keys, const cg_lb_service* values, size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    if (n && (!keys || !values)) fail(CG_INVALID_ARGUMENT, "NULL keys/values");
+    std::lock_guard<std::mutex> lk(e->mu);
+    LbMapState& p = get_lb(*e, lb_id);
+    std::map<LbMapState::Key, cg_lb_service> batch;
+    for (size_t i = 0; i < n; ++i) {
+      check_lb_addr(keys[i].family, values[i].target, "an IPv4 service value uses target bytes 0..3");
+      batch[make_lb_key(keys[i])] = values[i];
+    }
+    size_t fresh[2] = {0, 0};
+    for (const auto& kv : batch) fresh[kv.first[0] == 6] += !p.services.count(kv.first);
+    if (p.count_services(4) + fresh[0] > p.max_entries || p.count_services(6) + fresh[1] > p.max_entries)
+      fail(CG_MAP_FULL, "service map full (max_entries)");
+    for (const auto& kv : batch) p.services[kv.first] = kv.second;
+    p.dirty = true;
+  });
+}
+
+int cg_lb_map_service_delete(uint64_t h, uint32_t lb_id, const cg_lb_key* keys, size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    if (n && !keys) fail(CG_INVALID_ARGUMENT, "NULL keys");
+    std::lock_guard<std::mutex> lk(e->mu);
+    LbMapState& p = get_lb(*e, lb_id);
+    std::vector<LbMapState::Key> ks;
+    for (size_t i = 0; i < n; ++i) {
+      ks.push_back(make_lb_key(keys[i]));
+      if (!p.services.count(ks.back())) fail(CG_NOT_FOUND, "service map: no entry for key");
+    }
+    for (const auto& k : ks) p.services.erase(k);
+    p.dirty = true;
+  });
+}
+
+int cg_lb_map_service_lookup(uint64_t h, uint32_t lb_id, const cg_lb_key* key, cg_lb_service* value) {
+  return guarded([&] {
+    auto e = get(h);
+    if (!key || !value) fail(CG_INVALID_ARGUMENT, "NULL key/value");
+    std::lock_guard<std::mutex> lk(e->mu);
+    LbMapState& p = get_lb(*e, lb_id);
+    auto it = p.services.find(make_lb_key(*key));
+    if (it == p.services.end()) fail(CG_NOT_FOUND, "service map: no entry for key");
+    *value = it->second;
+  });
+}
+
+int cg_lb_map_service_dump(uint64_t h, uint32_t lb_id, cg_lb_key* keys, cg_lb_service* values, size_t cap, size_t* n) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    LbMapState& p = get_lb(*e, lb_id);
+    size_t i = 0;
+    for (const auto& [k, v] : p.services) {
+      if (i >= cap) break;
+      if (keys) keys[i] = LbMapState::key_of(k);
+      if (values) values[i] = v;
+      ++i;
+    }
+    if (n) *n = p.services.size();
+  });
+}
+
+int cg_lb_map_revnat_update(uint64_t h, uint32_t lb_id, const cg_lb_revnat_key* keys, const cg_lb_revnat* values,
+                            size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    if (n && (!keys || !values)) fail(CG_INVALID_ARGUMENT, "NULL keys/values");
+    std::lock_guard<std::mutex> lk(e->mu);
+    LbMapState& p = get_lb(*e, lb_id);
+    std::map<std::pair<uint8_t, uint16_t>, cg_lb_revnat> batch;
+    for (size_t i = 0; i < n; ++i) {
+      check_lb_addr(keys[i].family, values[i].address, "an IPv4 reverse NAT value uses address bytes 0..3");
+      if (values[i].pad) fail(CG_INVALID_ARGUMENT, "reverse NAT value pad must be 0");
+      batch[make_rn_key(keys[i])] = values[i];
+    }
+    size_t fresh[2] = {0, 0};
+    for (const auto& kv : batch) fresh[kv.first.first == 6] += !p.revnat.count(kv.first);
+    if (p.count_revnat(4) + fresh[0] > p.max_entries || p.count_revnat(6) + fresh[1] > p.max_entries)
+      fail(CG_MAP_FULL, "reverse NAT map full (max_entries)");
+    for (const auto& kv : batch) p.revnat[kv.first] = kv.second;
+    p.dirty = true;
+  });
+}
+
+int cg_lb_map_revnat_delete(uint64_t h, uint32_t lb_id, const cg_lb_revnat_key* keys, size_t n) {
+  return guarded([&] {
+    auto e = get(h);
+    if (n && !keys) fail(CG_INVALID_ARGUMENT, "NULL keys");
+    std::lock_guard<std::mutex> lk(e->mu);
+    LbMapState& p = get_lb(*e, lb_id);
+    std::vector<std::pair<uint8_t, uint16_t>> ks;
+    for (size_t i = 0; i < n; ++i) {
+      ks.push_back(make_rn_key(keys[i]));
+      if (!p.revnat.count(ks.back())) fail(CG_NOT_FOUND, "reverse NAT map: no entry for index");
+    }
+    for (const auto& k : ks) p.revnat.erase(k);
+    p.dirty = true;
+  });
+}
+
+int cg_lb_map_revnat_lookup(uint64_t h, uint32_t lb_id, const cg_lb_revnat_key* key, cg_lb_revnat* value) {
+  return guarded([&] {
+    auto e = get(h);
+    if (!key || !value) fail(CG_INVALID_ARGUMENT, "NULL key/value");
+    std::lock_guard<std::mutex> lk(e->mu);
+    LbMapState& p = get_lb(*e, lb_id);
+    auto it = p.revnat.find(make_rn_key(*key));
+    if (it == p.revnat.end()) fail(CG_NOT_FOUND, "reverse NAT map: no entry for index");
+    *value = it->second;
+  });
+}
+
+int cg_lb_map_revnat_dump(uint64_t h, uint32_t lb_id, cg_lb_revnat_key* keys, cg_lb_revnat* values, size_t cap,
+                          size_t* n) {
+  return guarded([&] {
+    auto e = get(h);
+    std::lock_guard<std::mutex> lk(e->mu);
+    LbMapState& p = get_lb(*e, lb_id);
+    size_t i = 0;
+    for (const auto& [k, v] : p.revnat) {
+      if (i >= cap) break;
+      if (keys) keys[i] = cg_lb_revnat_key{k.second, k.first, 0};
+      if (values) values[i] = v;
+      ++i;
+    }
+    if (n) *n = p.revnat.size();
   });
 }
 
@@ -1029,6 +1246,11 @@ struct FramesReq {
   uint32_t arr_id, ep_id, ipc_id;
   const uint32_t* ct_id;
   bool egress;
+  // the from-container program over a services map: the map, and the per-frame arrays only that program has
+  const uint32_t* lb_id = nullptr;
+  const uint32_t* hash = nullptr;
+  cg_ct_record* svc_recs = nullptr;
+  cg_lb_xlate* xlate = nullptr;
 };
 static void check_frames_args(uint32_t mode, const void* lxc, uint32_t ep_id, const void* labels, uint32_t ipc_id) {
   if ((mode & ~CG_L4_IGNORE_DROP) != CG_L4_INGRESS)
@@ -1048,6 +1270,8 @@ static void check_egress_args(uint32_t mode, const void* lxc, const void* labels
 }
 // The checks of every entry, in their order.  gpu: the entry launches; host: raw is read here (or staged from here).
 static void check_frames(Engine& e, const FramesReq& q, const FramesBatch& b, bool gpu, bool host) {
+  if (q.lb_id && (!q.ct_id || !q.ipc_id || b.labels))
+    fail(CG_INVALID_ARGUMENT, "the service steps need a conntrack map and the ipcache; dst_labels cannot name a backend");
   if (q.egress) check_egress_args(b.mode, b.lxc, b.labels, q.ipc_id, q.ct_id ? *q.ct_id : 0, b.recs);
   else check_frames_args(b.mode, b.lxc, q.ep_id, b.labels, q.ipc_id);
   if (gpu) e.require_gpu();
@@ -1059,7 +1283,8 @@ static void check_frames(Engine& e, const FramesReq& q, const FramesBatch& b, bo
 // headers, the ipcache, the conntrack map), taken under one hold of the handle lock; the launch holds all of them.
 struct FramesView {
   L4ArrView arr;
-  std::shared_ptr<DevTables> ep_keep, hdr_keep, ipc_keep, ct_keep;
+  std::shared_ptr<DevTables> ep_keep, hdr_keep, ipc_keep, ct_keep, lb_keep;
+  LbMapDev lb{};
   EpMapDev ep{};
   EpHdrDev hdr{};
   IpcacheDev ipc{};
@@ -1073,6 +1298,12 @@ static FramesView frames_view(Engine& e, const FramesReq& q) {
     if (p.dirty) p.rebuild(e);
     v.ct_keep = p.tab;
     v.ct = p.dev;
+  }
+  if (q.lb_id) {
+    LbMapState& p = get_lb(e, *q.lb_id);
+    if (p.dirty) p.rebuild(e);
+    v.lb_keep = p.tab;
+    v.lb = p.dev;
   }
   v.arr = l4_array_view_locked(e, q.arr_id);
   if (q.ep_id) {
@@ -1107,16 +1338,27 @@ static FramesView frames_view(Engine& e, const FramesReq& q) {
   }
   return v;
 }
-// The launch over device buffers d: the from-container program when the view holds headers.
-static void frames_launch(Engine& e, const FramesView& v, const FramesBatch& d, void* st) {
+// The launch over device buffers d: the from-container program when the view holds headers, the one with the
+// service steps when it holds a service map (x: that program's per-frame device arrays).
+struct SvcArrays {
+  const uint32_t* hash = nullptr;
+  cg_ct_record* svc_recs = nullptr;
+  cg_lb_xlate* xlate = nullptr;
+};
+static void frames_launch(Engine& e, const FramesView& v, const FramesBatch& d, const SvcArrays& x, void* st) {
   const IpcacheDev* ipc = v.ipc_keep ? &v.ipc : nullptr;
   const CtMapDev* ct = v.ct_keep ? &v.ct : nullptr;
-  if (v.hdr_keep)
+  if (v.lb_keep)
+    check_launch(launch_l4_frames_egress_svc(v.arr.dev, EpHdrSvcDev{v.hdr, v.lb, x.hash, (uint4*)x.svc_recs, (uint4*)x.xlate},
+                                             v.ipc, v.ct, d, st, e.cus),
+                 "l4 frames egress service kernel launch");
+  else if (v.hdr_keep)
     check_launch(launch_l4_frames_egress(v.arr.dev, v.hdr, ipc, ct, d, st, e.cus), "l4 frames egress kernel launch");
   else
     check_launch(launch_l4_frames(v.arr.dev, v.ep_keep ? &v.ep : nullptr, ipc, ct, d, st, e.cus),
                  ct ? "l4 frames conntrack kernel launch" : "l4 frames kernel launch");
   fence(v.ct_keep, st);
+  fence(v.lb_keep, st);
   v.arr.keep->own.fence.record(st);
   fence(v.ep_keep, st);
   fence(v.hdr_keep, st);
@@ -1128,14 +1370,14 @@ static void frames_dev(uint64_t h, const FramesReq& q, const FramesBatch& d, voi
   check_frames(*e, q, d, true, false);
   const FramesView v = frames_view(*e, q);
   e->set_device();
-  frames_launch(*e, v, d, stream_of(*e, stream));
+  frames_launch(*e, v, d, SvcArrays{q.hash, q.svc_recs, q.xlate}, stream_of(*e, stream));
 }
 
 static void* stage_in(StagingSlot& sl, int i, const void* src, size_t bytes);
 
 // The host entries' staging: the blob's window [raw_off[0], raw_off[n]), the offsets and the per-frame inputs go
 // up, the launch runs over the device copies, the results come back.
-static void frames_staged(Engine& e, const FramesView& v, const FramesBatch& b) {
+static void frames_staged(Engine& e, const FramesView& v, const FramesReq& q, const FramesBatch& b) {
   const size_t n = b.n;
   const uint64_t lo = b.off[0], bytes = b.off[n] > lo ? b.off[n] - lo : 0;
   e.set_device();
@@ -1152,24 +1394,35 @@ static void frames_staged(Engine& e, const FramesView& v, const FramesBatch& b) 
   d.out = (int32_t*)lease->dev_buf(5, n * 4);
   if (b.info) d.info = (cg_l4_frame_info*)lease->dev_buf(6, n * sizeof(cg_l4_frame_info));
   if (b.recs) d.recs = (cg_ct_record*)lease->dev_buf(7, n * sizeof(cg_ct_record));
-  frames_launch(e, v, d, (void*)st);
+  SvcArrays x;
+  if (q.hash) x.hash = (const uint32_t*)stage_in(*lease, 29, q.hash, n * 4);
+  if (q.svc_recs) x.svc_recs = (cg_ct_record*)lease->dev_buf(30, n * sizeof(cg_ct_record));
+  if (q.xlate) x.xlate = (cg_lb_xlate*)lease->dev_buf(31, n * sizeof(cg_lb_xlate));
+  frames_launch(e, v, d, x, (void*)st);
   int32_t* h_out = (int32_t*)lease->host_buf(5, n * 4);
   hip_check(hipMemcpyAsync(h_out, d.out, n * 4, hipMemcpyDeviceToHost, st), "D2H");
   void* h_info = b.info ? lease->host_buf(6, n * sizeof(cg_l4_frame_info)) : nullptr;
   if (b.info) hip_check(hipMemcpyAsync(h_info, d.info, n * sizeof(cg_l4_frame_info), hipMemcpyDeviceToHost, st), "D2H");
   void* h_recs = b.recs ? lease->host_buf(7, n * sizeof(cg_ct_record)) : nullptr;
   if (b.recs) hip_check(hipMemcpyAsync(h_recs, d.recs, n * sizeof(cg_ct_record), hipMemcpyDeviceToHost, st), "D2H");
+  void* h_srecs = q.svc_recs ? lease->host_buf(30, n * sizeof(cg_ct_record)) : nullptr;
+  if (q.svc_recs)
+    hip_check(hipMemcpyAsync(h_srecs, x.svc_recs, n * sizeof(cg_ct_record), hipMemcpyDeviceToHost, st), "D2H");
+  void* h_xl = q.xlate ? lease->host_buf(31, n * sizeof(cg_lb_xlate)) : nullptr;
+  if (q.xlate) hip_check(hipMemcpyAsync(h_xl, x.xlate, n * sizeof(cg_lb_xlate), hipMemcpyDeviceToHost, st), "D2H");
   hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
   memcpy(b.out, h_out, n * 4);
   if (b.info) memcpy(b.info, h_info, n * sizeof(cg_l4_frame_info));
   if (b.recs) memcpy(b.recs, h_recs, n * sizeof(cg_ct_record));
+  if (q.svc_recs) memcpy(q.svc_recs, h_srecs, n * sizeof(cg_ct_record));
+  if (q.xlate) memcpy(q.xlate, h_xl, n * sizeof(cg_lb_xlate));
 }
 
 static void frames_host(uint64_t h, const FramesReq& q, const FramesBatch& b) {
   auto e = get(h);
   check_frames(*e, q, b, true, true);
   const FramesView v = frames_view(*e, q);
-  if (b.n) frames_staged(*e, v, b);
+  if (b.n) frames_staged(*e, v, q, b);
 }
 
 int cg_l4_frames_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
@@ -1232,6 +1485,40 @@ int cg_l4_frames_egress_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode
   return guarded([&] {
     frames_host(h, {arr_id, 0, ipc_id, ct_id ? &ct_id : nullptr, true},
                 {raw, raw_off, n, lxc_ids, dst_labels, pkt_len, verdicts, info, recs, mode});
+  });
+}
+
+static FramesReq svc_req(uint32_t arr_id, uint32_t ipc_id, const uint32_t* ct_id, const uint32_t* lb_id,
+                         const uint32_t* hash, cg_ct_record* svc_recs, cg_lb_xlate* xlate) {
+  FramesReq q{arr_id, 0, ipc_id, *ct_id ? ct_id : nullptr, true};
+  q.lb_id = lb_id;
+  q.hash = hash;
+  q.svc_recs = svc_recs;
+  q.xlate = xlate;
+  return q;
+}
+
+int cg_l4_frames_egress_svc_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
+                                         const uint64_t* d_raw_off, size_t n, const uint16_t* d_lxc_ids,
+                                         const uint32_t* d_dst_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
+                                         uint32_t ct_id, uint32_t lb_id, const uint32_t* d_hash, int32_t* d_verdicts,
+                                         cg_l4_frame_info* d_info, cg_ct_record* d_records,
+                                         cg_ct_record* d_svc_records, cg_lb_xlate* d_xlate, void* stream) {
+  return guarded([&] {
+    frames_dev(h, svc_req(arr_id, ipc_id, &ct_id, &lb_id, d_hash, d_svc_records, d_xlate),
+               {d_raw, d_raw_off, n, d_lxc_ids, d_dst_labels, d_pkt_len, d_verdicts, d_info, d_records, mode}, stream);
+  });
+}
+
+int cg_l4_frames_egress_svc_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                          const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids,
+                                          const uint32_t* dst_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                          uint32_t ct_id, uint32_t lb_id, const uint32_t* hash, int32_t* verdicts,
+                                          cg_l4_frame_info* info, cg_ct_record* records, cg_ct_record* svc_records,
+                                          cg_lb_xlate* xlate) {
+  return guarded([&] {
+    frames_host(h, svc_req(arr_id, ipc_id, &ct_id, &lb_id, hash, svc_records, xlate),
+                {raw, raw_off, n, lxc_ids, dst_labels, pkt_len, verdicts, info, records, mode});
   });
 }
 
@@ -3080,6 +3367,12 @@ static void frames_eval_host(uint64_t h, const FramesReq& q, const FramesBatch& 
   EpMapDev E{};
   IpcacheDev ipc{};
   CtMapDev C{};
+  LbMapDev L{};
+  if (q.lb_id) {
+    LbMapState& p = get_lb(*e, *q.lb_id);
+    if (p.dirty) p.rebuild(*e);
+    L = p.host_view();
+  }
   if (q.ep_id) {
     EndpointMapState& p = get_ep(*e, q.ep_id);
     if (p.dirty) p.rebuild(*e);
@@ -3119,13 +3412,21 @@ static void frames_eval_host(uint64_t h, const FramesReq& q, const FramesBatch& 
       cg_l4_frame_info fi;
       CtRecWords r;
       uint32_t lo4 = 0;
-      b.out[i] = P::run(A, T, ipc, C, ld, len, lxc, label, plen, b.mode, &fi, &lo4, &r, count);
+      if constexpr (HasExtra<P>::value) {
+        typename P::Extra ex;
+        b.out[i] = P::run(A, T, ipc, C, ld, len, lxc, label, plen, b.mode, &fi, &lo4, &r, count, i, &ex);
+        P::store(T, i, ex);
+      } else {
+        b.out[i] = P::run(A, T, ipc, C, ld, len, lxc, label, plen, b.mode, &fi, &lo4, &r, count);
+      }
       if (b.info) b.info[i] = fi;
       if (P::kRecs && b.recs) memcpy(&b.recs[i], r.w, sizeof(cg_ct_record));
       if (l4_off) l4_off[i] = lo4;
     }
   };
-  if (q.egress)
+  if (q.lb_id)
+    loop(EgressSvcProg{}, EpHdrSvcDev{H, L, q.hash, (uint4*)q.svc_recs, (uint4*)q.xlate});
+  else if (q.egress)
     with_bools([&](auto kIpc, auto kCt) { loop(EgressProg<kIpc, kCt>{}, H); }, q.ipc_id != 0, q.ct_id != nullptr);
   else
     with_bools([&](auto kEp, auto kIpc, auto kCt) { loop(IngressProg<kEp, kIpc, kCt>{}, E); }, q.ep_id != 0,
@@ -3161,6 +3462,18 @@ int cg_diag_l4_frames_egress_eval_host(uint64_t h, uint32_t arr_id, uint32_t mod
   return guarded([&] {
     frames_eval_host(h, {arr_id, 0, ipc_id, ct_id ? &ct_id : nullptr, true},
                      {raw, raw_off, n, lxc_ids, dst_labels, pkt_len, verdicts, info, ct_recs, mode}, l4_off);
+  });
+}
+
+int cg_diag_l4_frames_egress_svc_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                           const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids,
+                                           const uint32_t* dst_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                           uint32_t ct_id, uint32_t lb_id, const uint32_t* hash, int32_t* verdicts,
+                                           cg_l4_frame_info* info, cg_ct_record* records, cg_ct_record* svc_records,
+                                           cg_lb_xlate* xlate, uint32_t* l4_off) {
+  return guarded([&] {
+    frames_eval_host(h, svc_req(arr_id, ipc_id, &ct_id, &lb_id, hash, svc_records, xlate),
+                     {raw, raw_off, n, lxc_ids, dst_labels, pkt_len, verdicts, info, records, mode}, l4_off);
   });
 }
 

@@ -89,7 +89,10 @@ struct CtMapState {
         const uint32_t cnt = (line[31] >> 16) & 0xFF;
         if (cnt == (uint32_t)S) continue;  // nb * S > n: a bucket with room exists
         for (int i = 0; i < W; ++i) line[W * cnt + i] = k.w[i];
-        line[W * S + cnt / 2] |= (uint32_t)kv.second.rev_nat_index << (16 * (cnt & 1));
+        // a TUPLE_F_SERVICE key is created with rev_nat_index 0 (lb.h:714-715 runs before :750): its 16 bits
+        // hold the entry's slave, which lb*_local reads (lb_walk.h)
+        const uint16_t v16 = kv.first[41] & CG_TUPLE_F_SERVICE ? kv.second.slave : kv.second.rev_nat_index;
+        line[W * S + cnt / 2] |= (uint32_t)v16 << (16 * (cnt & 1));
         line[31] += 1u << 16;
         if (kv.second.flags & CG_CT_E_LB_LOOPBACK) line[31] |= 1u << (24 + cnt);
         if (p > *probes) *probes = p;

@@ -18,8 +18,9 @@
 //   v4  7 keys of 16 B {daddr, saddr, dport, sport, nexthdr, flags, scope}:
 //       struct ipv4_ct_tuple as the datapath stores it (lib/common.h:359-367)
 //       and the 16-bit scope behind it; words 28..31 hold the 7 u16
-//       rev_nat_index values, the slot count (byte 126) and the lb_loopback
-//       bits (byte 127).
+//       rev_nat_index values (for a TUPLE_F_SERVICE key, whose rev_nat_index
+//       is always 0, the entry's slave), the slot count (byte 126) and the
+//       lb_loopback bits (byte 127).
 //   v6  3 keys of 40 B {daddr[16], saddr[16], dport, sport, nexthdr, flags,
 //       scope}: struct ipv6_ct_tuple (:338-346) and the scope; words 30..31
 //       hold 3 u16 rev_nat_index values, the count and the loopback bits.
@@ -223,6 +224,64 @@ CG_HDI int32_t ct_tail(const CtMapDev& C, Ld ld, uint32_t family, uint32_t proto
     for (int i = 0; i < 4; ++i) {
       k.w[i] = ld(kEthHlen + 24 + 4 * i);
       k.w[4 + i] = ld(kEthHlen + 8 + 4 * i);
+    }
+    k.w[8] = ports;
+    k.w[9] = last;
+    state = ct_lookup<kCt6Words, kCt6Slots>(C.t6, C.mask6, C.probes6, &k, &val);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.w[4 + i] = k.w[i];
+    r.w[12] = k.w[8];
+    r.w[13] = k.w[9];
+  }
+  // the record's tuple carries the datapath's flags; the kind has its own byte
+  r.w[13] = r.w[13] & 0xFFFFu & ~(kCtKindBit << 8);
+  r.w[14] = scope | family << 16 | kind << 24;
+  const bool reply = state == CG_CT_STATE_REPLY || state == CG_CT_STATE_RELATED;
+  uint32_t op = CG_CT_OP_NONE;
+  int32_t out = v;
+  if (reply) out = 0;
+  else if (v < 0) op = state == CG_CT_STATE_ESTABLISHED ? CG_CT_OP_DELETE : CG_CT_OP_NONE;
+  else if (state == CG_CT_STATE_NEW) op = CG_CT_OP_CREATE;
+  r.w[0] = state | op << 8 | (val >> 16) << 16 | dir << 24;
+  r.w[1] = val & 0xFFFF;
+  *rec = r;
+  return out;
+}
+
+// ct_tail over a tuple the caller holds instead of the frame's own: ports and
+// tf as ct_ports gives them, aw(src, i) word i of the source / destination
+// address.  The from-container program with services (egress_walk.h) passes
+// the translated tuple.  It restates ct_tail's body rather than sharing it:
+// the kernels built on ct_tail keep their code, and their register counts,
+// as they are.
+template <class Aw>
+CG_HDI int32_t ct_tail_tuple(const CtMapDev& C, Aw aw, uint32_t ports, uint32_t tf, uint32_t family, uint32_t proto,
+                             uint32_t lxc, uint32_t dir, int32_t v, CtRecWords* rec) {
+  CtRecWords r;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) r.w[i] = 0;
+  const uint32_t scope = C.global ? 0u : lxc;
+  const uint32_t kind = proto == 6 ? CG_CT_MAP_TCP : CG_CT_MAP_ANY;
+  tf |= dir;
+  const uint32_t last = proto | (tf | (kind == CG_CT_MAP_ANY ? kCtKindBit : 0u)) << 8 | scope << 16;
+  uint32_t state, val = 0;
+  if (family == 4) {
+    CtKey<kCt4Words> k;
+    k.w[0] = aw(false, 0);  // daddr, saddr: the header's bytes as they lie
+    k.w[1] = aw(true, 0);
+    k.w[2] = ports;
+    k.w[3] = last;
+    state = ct_lookup<kCt4Words, kCt4Slots>(C.t4, C.mask4, C.probes4, &k, &val);
+    r.w[4] = k.w[0];
+    r.w[8] = k.w[1];
+    r.w[12] = k.w[2];
+    r.w[13] = k.w[3];
+  } else {
+    CtKey<kCt6Words> k;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      k.w[i] = aw(false, i);
+      k.w[4 + i] = aw(true, i);
     }
     k.w[8] = ports;
     k.w[9] = last;

@@ -35,6 +35,16 @@ CG_HD inline uint4 load16(const void* p) {
 #endif
 }
 
+// 16 bytes of a caller's record array in one store (a caller's host buffer is
+// aligned for its element type only: the host copies).
+CG_HD inline void store16(void* p, const uint4& v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  *reinterpret_cast<uint4*>(p) = v;
+#else
+  memcpy(p, &v, sizeof(v));
+#endif
+}
+
 // ------------------------------------------------------------------ L4 ----
 // Cuckoo hash of policy keys (2 choices × 64-B buckets of 4 slots).
 // slot = {u64 key, u32 val, u32 pad}; key = sec_label | dport<<32 | proto<<48 |

@@ -112,8 +112,9 @@ class PinnedMem {
 // device buffers and pinned host buffers, so host calls make no hipMalloc /
 // hipFree and copy with async DMA instead of pageable hipMemcpy.
 struct StagingSlot {
-  static constexpr int kBufs = 29;  // 0..7 host staging, 8..18 the raw HTTP path's workspace, 19..26 its device-layout
-                                    // sequence's, 27-28 the Kafka decoder's inflate arena and deferred list
+  static constexpr int kBufs = 32;  // 0..7 host staging, 8..18 the raw HTTP path's workspace, 19..26 its device-layout
+                                    // sequence's, 27-28 the Kafka decoder's inflate arena and deferred list,
+                                    // 29-31 the frames route's hash, service records and translation records
   void* stream = nullptr;  // hipStream_t
   DevMem dev[kBufs];
   PinnedMem host[kBufs];
@@ -161,6 +162,7 @@ struct PrefilterState;
 struct IpcacheState;
 struct EndpointMapState;
 struct CtMapState;
+struct LbMapState;
 struct SelcacheState;
 struct HttpSnapshot;
 struct KafkaSnapshot;
@@ -180,6 +182,7 @@ struct Engine {
   std::map<uint32_t, std::unique_ptr<IpcacheState>> ipcaches;
   std::map<uint32_t, std::unique_ptr<EndpointMapState>> epmaps;  // cilium_lxc (endpoint_map.h)
   std::map<uint32_t, std::unique_ptr<CtMapState>> ctmaps;        // the conntrack maps (ct_map.h)
+  std::map<uint32_t, std::unique_ptr<LbMapState>> lbmaps;        // the service maps (lb_map.h)
   std::map<uint32_t, std::unique_ptr<SelcacheState>> selcaches;
   std::shared_ptr<HttpSnapshot> http;
   std::shared_ptr<KafkaSnapshot> kafka;

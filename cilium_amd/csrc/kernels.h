@@ -6,6 +6,7 @@
 
 #include "ct_walk.h"
 #include "dev_types.h"
+#include "lb_walk.h"
 
 namespace cg {
 
@@ -49,6 +50,10 @@ int launch_l4_frames(const L4ArrDev& A, const EpMapDev* E, const IpcacheDev* ipc
 // array's endpoint headers; ipc NULL: labels are the destination identities.
 int launch_l4_frames_egress(const L4ArrDev& A, const EpHdrDev& H, const IpcacheDev* ipc, const CtMapDev* C,
                             const FramesBatch& b, void* stream, int cus);
+// The same program over a services map (lb_walk.h): T carries the headers, the
+// service tables and the per-frame hash / svc_records / xlate arrays.
+int launch_l4_frames_egress_svc(const L4ArrDev& A, const EpHdrSvcDev& T, const IpcacheDev& ipc, const CtMapDev& C,
+                                const FramesBatch& b, void* stream, int cus);
 int launch_lpm(const LpmDev& t, bool v4_filter, bool v6_filter, const uint32_t* v4, size_t n4,
                uint8_t* out4, const uint8_t* v6, size_t n6, uint8_t* out6, void* stream, int cus);
 // order (optional): out[order[slot]] instead of out[slot] (request order;

@@ -10,7 +10,8 @@
 // l4_frames_kernel<P> is that lane for every program of frame_progs.h: the
 // ingress program, the same with the conntrack lookup of ct_walk.h between the
 // walk and the verdict, and the endpoint's from-container program
-// (egress_walk.h), each in its resolver combinations: twelve kernels.
+// (egress_walk.h), each in its resolver combinations: twelve kernels; and the
+// from-container program over a services map (lb_walk.h), the thirteenth.
 #include <hip/hip_runtime.h>
 
 #include <map>
@@ -76,12 +77,19 @@ __global__ __launch_bounds__(kFrmThreads) void l4_frames_kernel(
     cg_l4_frame_info fi;
     CtRecWords r;
     uint32_t l4_off;
-    const int32_t v = P::run(
-        A, T, ipc, C, [&](uint32_t o) { return frame_word(base + o, lo, hi); }, len, id, label, plen, mode, &fi,
-        &l4_off, &r, [&](const L4Dev& t, uint32_t entry) {
-          atomicAdd(&t.counters[2 * entry], 1ULL);
-          atomicAdd(&t.counters[2 * entry + 1], (unsigned long long)plen);
-        });
+    const auto ld = [&](uint32_t o) { return frame_word(base + o, lo, hi); };
+    const auto count = [&](const L4Dev& t, uint32_t entry) {
+      atomicAdd(&t.counters[2 * entry], 1ULL);
+      atomicAdd(&t.counters[2 * entry + 1], (unsigned long long)plen);
+    };
+    int32_t v;
+    if constexpr (HasExtra<P>::value) {  // the program with services: its own per-frame outputs go out here
+      typename P::Extra ex;
+      v = P::run(A, T, ipc, C, ld, len, id, label, plen, mode, &fi, &l4_off, &r, count, i, &ex);
+      P::store(T, i, ex);
+    } else {
+      v = P::run(A, T, ipc, C, ld, len, id, label, plen, mode, &fi, &l4_off, &r, count);
+    }
     __builtin_nontemporal_store(v, out + i);
     if (info) {
       uint4 q;
@@ -143,6 +151,11 @@ int launch_l4_frames_egress(const L4ArrDev& A, const EpHdrDev& H, const IpcacheD
                             const FramesBatch& b, void* stream, int cus) {
   return with_bools([&](auto kIpc, auto kCt) { return launch<EgressProg<kIpc, kCt>>(A, H, ipc, C, b, stream, cus); },
                     ipc != nullptr, C != nullptr);
+}
+
+int launch_l4_frames_egress_svc(const L4ArrDev& A, const EpHdrSvcDev& T, const IpcacheDev& ipc, const CtMapDev& C,
+                                const FramesBatch& b, void* stream, int cus) {
+  return launch<EgressSvcProg>(A, T, &ipc, &C, b, stream, cus);
 }
 
 }  // namespace cg

@@ -464,12 +464,12 @@ typedef struct {
   uint8_t state; /* CG_CT_STATE_* */
   uint8_t op;    /* CG_CT_OP_* */
   uint8_t loopback;
-  uint8_t pad0; /* dir: 0 ingress, 1 egress (cg_l4_frames_egress_verdicts_*) */
+  uint8_t pad0; /* dir: 0 ingress, 1 egress (cg_l4_frames_egress_verdicts_*), 2 service */
   uint16_t rev_nat_index;
-  uint16_t pad1;
-  uint32_t pad2[2]; /* [0]: src_sec_id of an egress record (the header's seclabel) */
+  uint16_t pad1;    /* the slave (cg_l4_frames_egress_svc_verdicts_*) */
+  uint32_t pad2[2]; /* [0]: src_sec_id of an egress record (the header's seclabel); [1]: ct_state.addr */
   cg_ct_key key;
-  uint32_t pad3;
+  uint32_t pad3; /* ct_state.svc_addr */
 } cg_ct_record;
 /* ct_id: the conntrack map; d_records / records may be NULL. */
 int cg_l4_frames_ct_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
@@ -490,6 +490,17 @@ int cg_l4_frames_ct_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, co
  *    so a duplicate CREATE leaves one pair;
  *  - DELETE: the key is removed; a key already gone is not an error
  *    (ct_delete* ignores it).
+ *  - the fields cg_l4_frames_egress_svc_verdicts_* fill, all 0 in every other
+ *    record: CREATE writes rev_nat_index, loopback (lb_loopback) and pad1
+ *    (slave) into both entries.  pad0 == 2 (CT_SERVICE) creates as any dir
+ *    that is not CT_INGRESS does: tx counters, src_sec_id 0, the related key
+ *    with TUPLE_F_SERVICE | TUPLE_F_RELATED.  A v4 egress CREATE with pad2[1]
+ *    (ct_state.addr) != 0 also writes ct_create4's second entry
+ *    (conntrack.h:725-753): the key with daddr = addr, and on loopback flags
+ *    = TUPLE_F_IN and saddr = pad3 (svc_addr); the three keys fit together or
+ *    none is written;
+ *  - UPDATE_SLAVE (ct_update{4,6}_slave): sets slave = pad1 on the key; a
+ *    missing key is ignored.
  * results[i] (may be NULL): 0, or CG_DROP_CT_CREATE_FAILED when the frame's
  * new keys did not fit under max_entries; neither key is written then. */
 int cg_ct_map_apply(uint64_t h, uint32_t ct_id, const cg_ct_record* records, size_t n, const uint32_t* pkt_len,
@@ -529,10 +540,11 @@ int cg_policy_array_get_header(uint64_t h, uint32_t arr_id, uint16_t lxc_id, cg_
  * handle_ipv4_from_lxc (:432-570), handle_ipv6 + ipv6_l3_from_lxc (:389-416,
  * :114-266) — per frame of a blob, on the map and the header in the
  * endpoint's slot of the policy array.  The program is the one built with
- * CONNTRACK, LB_L3 and LB_L4 over an empty services map: lb{4,6}_lookup_service
- * finds nothing, lb*_local and lb*_rev_nat never run, ct_state_new.rev_nat_index
- * stays 0.  MAC rewrite, forwarding and local delivery behind the verdict are
- * not modelled.
+ * CONNTRACK, LB_L3 and LB_L4; these entries run it over an empty services map
+ * (lb{4,6}_lookup_service finds nothing, lb*_local and lb*_rev_nat never run,
+ * ct_state_new.rev_nat_index stays 0), cg_l4_frames_egress_svc_verdicts_* below
+ * over a cg_lb_map.  MAC rewrite, forwarding and local delivery behind the
+ * verdict are not modelled.
  *
  * mode: CG_L4_EGRESS [| CG_L4_IGNORE_DROP]; anything else is
  * CG_INVALID_ARGUMENT.  lxc_ids is mandatory (the program hangs on the
@@ -630,6 +642,175 @@ int cg_l4_frames_egress_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode
                                       const uint32_t* dst_labels, uint32_t ipc_id, const uint32_t* pkt_len,
                                       uint32_t ct_id, int32_t* verdicts, cg_l4_frame_info* info,
                                       cg_ct_record* records);
+
+/* Service load-balancing: cilium_lb{4,6}_services and
+ * cilium_lb{4,6}_reverse_nat (bpf/lib/lb.h:38-84, pkg/maps/lbmap) of one node
+ * in one object, with the node constant IPV4_LOOPBACK (node_config.h; network
+ * order, 0 is legal: the loopback case then rewrites no source).
+ *  - A service key is struct lb{4,6}_key {address, dport (network order),
+ *    slave}: slave 0 is the master, whose value's `count` says how many slaves
+ *    follow; slaves 1..count carry the backends.  A value is struct
+ *    lb{4,6}_service {target, port (network order), count, rev_nat_index,
+ *    weight}.  weight is stored and dumped and never read: the datapath's use
+ *    of the _rr_seq maps is compiled out (lb.h:139, :173), so they are not built.
+ *  - A reverse-NAT entry is u16 index -> {address, port (network order)}.
+ *  - max_entries bounds each of the four maps by itself; 0 = 65536
+ *    (CILIUM_LB_MAP_MAX_ENTRIES).  Updates are all-or-nothing per call:
+ *    CG_INVALID_ADDRESS for a family other than 4 / 6, CG_INVALID_ARGUMENT for a
+ *    v4 key or value with address bytes past the fourth or a non-zero pad,
+ *    CG_MAP_FULL when the batch would exceed max_entries; nothing is applied.
+ *    A key given twice keeps its last value.  delete: CG_NOT_FOUND (nothing
+ *    deleted) if any key is absent.
+ *  - Dump order: services by (family, address bytes, dport's two bytes as
+ *    stored, slave as a number); reverse NAT by (family, index).
+ *  - On the device: an exact-match table per family in HBM and the reverse-NAT
+ *    entries as a dense array indexed by the u16, published by
+ *    swap; a verdict call takes its snapshot under the same hold of the handle
+ *    lock as the array's, the ipcache's and the conntrack map's. */
+#define CG_LB_MAP_MAX_ENTRIES 65536u
+typedef struct {
+  uint8_t address[16]; /* network byte order; v4 uses [0..3], the rest 0 */
+  uint16_t dport;      /* network byte order, as stored; 0: the L3 service */
+  uint16_t slave;      /* 0: the master */
+  uint8_t family;      /* 4 or 6 */
+  uint8_t pad[3];
+} cg_lb_key; /* 24 bytes */
+typedef struct {
+  uint8_t target[16];
+  uint16_t port; /* network byte order; 0: the port is not rewritten */
+  uint16_t count;
+  uint16_t rev_nat_index;
+  uint16_t weight;
+} cg_lb_service; /* 24 bytes */
+typedef struct {
+  uint16_t index;
+  uint8_t family;
+  uint8_t pad;
+} cg_lb_revnat_key; /* 4 bytes */
+typedef struct {
+  uint8_t address[16];
+  uint16_t port;
+  uint16_t pad;
+} cg_lb_revnat; /* 20 bytes */
+int cg_lb_map_create(uint64_t h, uint32_t max_entries, uint32_t ipv4_loopback, uint32_t* lb_id);
+int cg_lb_map_destroy(uint64_t h, uint32_t lb_id);
+int cg_lb_map_set_loopback(uint64_t h, uint32_t lb_id, uint32_t ipv4_loopback);
+int cg_lb_map_service_update(uint64_t h, uint32_t lb_id, const cg_lb_key* keys, const cg_lb_service* values, size_t n);
+int cg_lb_map_service_delete(uint64_t h, uint32_t lb_id, const cg_lb_key* keys, size_t n);
+int cg_lb_map_service_lookup(uint64_t h, uint32_t lb_id, const cg_lb_key* key, cg_lb_service* value);
+int cg_lb_map_service_dump(uint64_t h, uint32_t lb_id, cg_lb_key* keys, cg_lb_service* values, size_t cap, size_t* n);
+int cg_lb_map_revnat_update(uint64_t h, uint32_t lb_id, const cg_lb_revnat_key* keys, const cg_lb_revnat* values,
+                            size_t n);
+int cg_lb_map_revnat_delete(uint64_t h, uint32_t lb_id, const cg_lb_revnat_key* keys, size_t n);
+int cg_lb_map_revnat_lookup(uint64_t h, uint32_t lb_id, const cg_lb_revnat_key* key, cg_lb_revnat* value);
+int cg_lb_map_revnat_dump(uint64_t h, uint32_t lb_id, cg_lb_revnat_key* keys, cg_lb_revnat* values, size_t cap,
+                          size_t* n);
+
+/* cg_l4_frames_egress_verdicts_* over a services map: the from-container
+ * program with lb{4,6}_lookup_service, lb{4,6}_local and lb*_xlate (bpf/lib/lb.h;
+ * bpf_lxc.c:468-484, :148-170) in their place between steps 7 and 8 of the
+ * order above, one launch.  The arguments are those entries' plus lb_id, the
+ * map, and hash; ct_id and ipc_id are mandatory and dst_labels must be NULL
+ * (CG_INVALID_ARGUMENT otherwise; an unknown lb_id is CG_NOT_FOUND):
+ * lb*_local is conntrack, and the backend's identity exists only after the
+ * translation.  The frame blob is read-only: the translation lives in the
+ * tuple the later steps take.  Checksums and store errors are not modelled.
+ *
+ *  7a. the service key {tuple.daddr, dport, slave 0}: dport is the two bytes at
+ *      l4_off + 2 for TCP / UDP, 0 for ICMP / ICMPv6.  Any other protocol
+ *      (DROP_UNKNOWN_L4) skips 7b-7e, as the reference's goto does;
+ *  7b. lb*_lookup_service (lb.h:604-635, :351-380): with dport != 0 the L4
+ *      master, which counts only with count != 0; otherwise key.dport is zeroed,
+ *      and stays zeroed, and the L3 master is looked up, again only with count
+ *      != 0.  A miss leaves the program exactly as it runs without services;
+ *  7c. lb*_local: ct_lookup* as CT_SERVICE — the tuple's flags are
+ *      TUPLE_F_SERVICE [| RELATED], ports and ICMP rules those of the head of
+ *      ct_lookup*, one lookup of the tuple as loaded, no reversal
+ *      (conntrack.h:580, :423), map kind and scope those of the egress lookup.
+ *      A frame for which the head of ct_lookup* fails (e.g. TCP with l4_off + 4
+ *      <= len < l4_off + 14) leaves with CG_DROP_NO_SERVICE, not the head's own
+ *      code.  CT_NEW: slave = hash % count + 1, op CREATE.  REPLY / RELATED:
+ *      the slave is the matched entry's;
+ *  7d. lb*_lookup_slave with key.slave = slave; any entry counts.  On a miss
+ *      lb*_lookup_service runs again with the key as it now stands, slave
+ *      number included (lb.h:737-744): with key.dport != 0, {daddr, dport,
+ *      slave} (which just missed) and then {daddr, 0, slave} with count != 0;
+ *      with key.dport == 0 nothing new.  A hit re-selects the slave from that
+ *      entry's count (op UPDATE_SLAVE) and that entry is the one translated
+ *      to; a miss is CG_DROP_NO_SERVICE.  Over maps the control plane wrote
+ *      (count 0 in every slave slot) a flow whose slave slot has gone therefore
+ *      leaves with CG_DROP_NO_SERVICE;
+ *  7e. rev_nat_index = svc.rev_nat_index; the new destination is svc.target.
+ *      v4 with saddr == svc.target (lb.h:761-770): the new source is
+ *      IPV4_LOOPBACK, loopback = 1, ct_state.addr = IPV4_LOOPBACK, svc_addr =
+ *      saddr, and tuple.daddr stays the VIP; otherwise tuple.daddr = target
+ *      (v4: ct_state.addr = target).  TCP / UDP with svc.port != 0 and
+ *      key.dport != svc.port (key.dport is 0 after the L3 fallback): dport =
+ *      svc.port;
+ *  8-12 as above on the translated tuple: the CT_EGRESS lookups use tuple.daddr
+ *      after 7e and the rewritten dport, the ipcache resolves tuple.daddr after
+ *      7e, policy_can_egress takes that identity and that dport, and an egress
+ *      CREATE record carries ct_state_new: rev_nat_index, loopback, pad1 =
+ *      slave, pad2[1] = ct_state.addr, pad3 = svc_addr;
+ *  reverse NAT: REPLY / RELATED with the matched entry's rev_nat_index != 0
+ *      (bpf_lxc.c:554-565, :248-262) reports what lb{4,6}_rev_nat(…, flags 0)
+ *      would write: the entry's address as the new source, its port as the new
+ *      sport for TCP / UDP when non-zero, on v4 loopback the old source as the
+ *      new destination.  A missing entry reports nothing; the verdict does not
+ *      change.  The ingress program's lb4_rev_nat stays out.
+ *
+ * hash[i] (may be NULL) stands for get_hash_recalc(skb), the kernel's flow
+ * hash, which the engine cannot reproduce; NULL: cg_diag_ct_hash of the
+ * frame's CT_SERVICE key.
+ *
+ * records: the CT_EGRESS step's, as above.  svc_records (may be NULL): the
+ * CT_SERVICE step's cg_ct_record per frame, all-zero when the service steps
+ * did not run, missed, or left before the lookup: state, op, the key with
+ * TUPLE_F_SERVICE, pad0 = 2 (CT_SERVICE), pad1 = the slave.  A CT_NEW frame whose
+ * slave is re-selected in 7d gets one op, CREATE, with the slave it ends with.
+ * xlate (may be NULL): a cg_lb_xlate per frame.  cg_ct_map_apply takes
+ * svc_records first, then records.  The reference fails closed when the
+ * service entry cannot be created; here the create happens in apply, after the
+ * verdict, and the failure shows in apply's results — the divergence the
+ * egress CREATE already has. */
+#define CG_DROP_NO_SERVICE (-158) /* bpf/lib/common.h:265 */
+#define CG_CT_OP_UPDATE_SLAVE 3u  /* ct_update{4,6}_slave: sets slave on an existing key */
+#define CG_LB_NONE 0u       /* the service steps did not run */
+#define CG_LB_MISS 1u       /* no service for the destination */
+#define CG_LB_TRANSLATED 2u
+#define CG_LB_NO_SERVICE 3u /* the frame left with CG_DROP_NO_SERVICE */
+#define CG_LB_F_L3 0x01u       /* the master that matched is the L3 one (key.dport == 0) */
+#define CG_LB_F_PORT 0x02u     /* the destination port was rewritten */
+#define CG_LB_F_LOOPBACK 0x04u /* the v4 loopback case */
+#define CG_LB_F_REVNAT 0x08u   /* a reverse translation is reported */
+/* 48 bytes, written as three 16-byte pieces.  The addresses and ports are the
+ * packet's after the translation (status TRANSLATED) or after the reverse
+ * translation (CG_LB_F_REVNAT); all four are 0 otherwise, as is family. */
+typedef struct {
+  uint8_t status; /* CG_LB_* */
+  uint8_t flags;  /* CG_LB_F_* */
+  uint16_t slave;
+  uint16_t rev_nat_index;
+  uint16_t dport; /* network byte order */
+  uint16_t sport;
+  uint8_t family;
+  uint8_t pad0;
+  uint32_t pad1;
+  uint8_t daddr[16];
+  uint8_t saddr[16];
+} cg_lb_xlate;
+int cg_l4_frames_egress_svc_verdicts_dev(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* d_raw,
+                                         const uint64_t* d_raw_off, size_t n, const uint16_t* d_lxc_ids,
+                                         const uint32_t* d_dst_labels, uint32_t ipc_id, const uint32_t* d_pkt_len,
+                                         uint32_t ct_id, uint32_t lb_id, const uint32_t* d_hash, int32_t* d_verdicts,
+                                         cg_l4_frame_info* d_info, cg_ct_record* d_records,
+                                         cg_ct_record* d_svc_records, cg_lb_xlate* d_xlate, void* stream);
+int cg_l4_frames_egress_svc_verdicts_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                          const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids,
+                                          const uint32_t* dst_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                          uint32_t ct_id, uint32_t lb_id, const uint32_t* hash, int32_t* verdicts,
+                                          cg_l4_frame_info* info, cg_ct_record* records, cg_ct_record* svc_records,
+                                          cg_lb_xlate* xlate);
 
 /* ======================================================================== */
 /* LPM: XDP CIDR prefilter — bpf/bpf_xdp.c:88-184,                           */
@@ -1415,6 +1596,14 @@ int cg_diag_l4_frames_egress_eval_host(uint64_t h, uint32_t arr_id, uint32_t mod
 /* The conntrack tables' own hash of each key (before the bucket mask), and
  * the built tables' shape: buckets and the recorded probe bound per family
  * ([0] v4, [1] v6).  For tests that build probe chains. */
+/* cg_l4_frames_egress_svc_verdicts_* on the host: the kernel's own walk
+ * (egress_walk.h, lb_walk.h) per frame over the maps' host views. */
+int cg_diag_l4_frames_egress_svc_eval_host(uint64_t h, uint32_t arr_id, uint32_t mode, const uint8_t* raw,
+                                           const uint64_t* raw_off, size_t n, const uint16_t* lxc_ids,
+                                           const uint32_t* dst_labels, uint32_t ipc_id, const uint32_t* pkt_len,
+                                           uint32_t ct_id, uint32_t lb_id, const uint32_t* hash, int32_t* verdicts,
+                                           cg_l4_frame_info* info, cg_ct_record* records, cg_ct_record* svc_records,
+                                           cg_lb_xlate* xlate, uint32_t* l4_off);
 int cg_diag_ct_hash(const cg_ct_key* keys, size_t n, uint32_t* hashes);
 int cg_diag_ct_map_info(uint64_t h, uint32_t ct_id, uint32_t buckets[2], uint32_t probes[2]);
 /* The ipcache tables walked on the host exactly as ipcache_kernel does. */

@@ -25,7 +25,9 @@ configs, one JSON line each (bench.py covers config 5, the 10K-rule HTTP set):
   tuples and against host extraction + upload + that route; with a conntrack
   map; and the egress program (l4_frames_kernel<EgressProg>) on an egress batch of
   the same shape, with and without conntrack and records, as ratios to the
-  ingress kernels of the same run
+  ingress kernels of the same run; and that program over a synthetic service
+  map (l4_frames_kernel<EgressSvcProg>), on the batch as it is and with a quarter
+  of its frames snapped to VIPs, as ratios to the egress kernel with records
 
 Inputs are resident in HBM before timing; kernels are timed with HIP events
 on their stream.  Each line carries the kernel's HBM roofline (algorithmic
@@ -363,6 +365,87 @@ def _bench_l4_frames_ct(torch, dev, stream, cl, args, arr, kw, raw, off, plen, d
                              "over_no_conntrack": sec_rec / sec_plain}}
 
 
+def _bench_l4_frames_services(torch, dev, stream, cl, args, arr, ct, kw, hkw, raw, off, winfo, l4o, d_off, d_out, D, n,
+                              reps, sec_egress_rec):
+    """l4_frames_kernel<EgressSvcProg> on _bench_l4_frames_egress' batch and conntrack
+    map, over a synthetic service map: 4,096 IPv4 L3 services and 1,024 IPv6
+    ones of four backends each (backends drawn from the batch's own
+    destinations, so the ipcache knows them), every second one rewriting the
+    port.  Two batches: the egress batch as it is, where no frame hits a
+    service, and the same frames with a quarter of the TCP / UDP / ICMP frames
+    that reach the policy snapped to a VIP.  Each is checked against
+    cg_diag_l4_frames_egress_svc_eval_host over the first copy, then timed
+    three ways: verdicts only, plus records, plus service records and
+    translation records.  The ratios are to l4_frames_kernel<EgressProg<ipc,
+    ct>> with records in this same run."""
+    from cilium_amd.classifier import CT_RECORD_DTYPE, LB_XLATE_DTYPE
+    rng = np.random.default_rng(0x5C)
+    svc = cl.service_map(ipv4_loopback="169.254.42.1")
+    walked = np.flatnonzero(winfo["t"]["flags"] != 0)
+    b = off[:-1].astype(np.int64)
+    fam = winfo["family"]
+    w4, w6 = walked[fam[walked] == 4], walked[fam[walked] == 6]
+    be4 = np.unique(raw[b[w4][:, None] + np.arange(30, 34)], axis=0)
+    be6 = np.unique(raw[b[w6][:, None] + np.arange(38, 54)], axis=0)
+    keys, vals = [], []
+    vips = {4: [], 6: []}
+    for f, nsvc, pool in ((4, 4096, be4), (6, 1024, be6)):
+        for i in range(nsvc):
+            vip = bytes([198, 18, i >> 8, i & 255]) if f == 4 else bytes([0xfd, 0x96] + [0] * 12 + [i >> 8, i & 255])
+            vips[f].append(vip)
+            keys.append(svc.key(vip, 0, 0))
+            vals.append(svc.value(None, 0, 4, 0, 0))
+            for s_ in range(1, 5):
+                keys.append(svc.key(vip, 0, s_))
+                port = 0 if i % 2 else int(rng.integers(1024, 65535))
+                vals.append(svc.value(bytes(pool[rng.integers(0, len(pool))]), port, 0, 1 + (i & 0x3FFF), 0))
+    svc.update(keys, vals)
+    svc.update_revnat(np.arange(1, 4097), vips[4], np.zeros(4096, np.uint16))
+    d_rec, d_srec = (torch.empty((n, 64), dtype=torch.uint8, device=dev) for _ in range(2))
+    d_xl = torch.empty((n, 48), dtype=torch.uint8, device=dev)
+    out = {"kernel": "l4_frames_kernel<EgressSvcProg>", "services": {"v4": 4096, "v6": 1024, "backends_each": 4},
+           "yardstick": "l4_frames_kernel<EgressProg<ipc, ct>> with records, this run",
+           "yardstick_kernel_ms": sec_egress_rec * 1e3}
+    snapped = raw.copy()
+    pick = walked[rng.random(len(walked)) < 0.25]
+    for f, do, size in ((4, 30, 4), (6, 38, 16)):
+        m = pick[fam[pick] == f]
+        choice = np.array([list(v) for v in vips[f]], np.uint8)[rng.integers(0, len(vips[f]), len(m))]
+        snapped[b[m][:, None] + np.arange(do, do + size)] = choice
+    for name, blob_ in (("no_service_hit", raw), ("quarter_snapped_to_vips", snapped)):
+        d_raw = tile_dev(torch, blob_, reps, dev)
+        call = lambda **extra: arr.frame_egress_verdicts_dev(d_raw, d_off, n, d_out, conntrack=ct, services=svc,  # noqa: E731
+                                                             **extra, **kw)
+        arr.frame_egress_verdicts_dev(d_raw, d_off, D, d_out, conntrack=ct, services=svc, d_records=d_rec,
+                                      d_svc_records=d_srec, d_xlate=d_xl, **kw)
+        stream.synchronize()
+        want, _, wrec, wsrec, wxl = arr.frame_egress_eval_host_diag(blob_, off, info=True, conntrack=ct, services=svc,
+                                                                    xlate=True, **hkw)
+        assert np.array_equal(d_out[:D].cpu().numpy(), want), "service verdicts differ from the host evaluator"
+        assert d_rec[:D].cpu().numpy().tobytes() == wrec.tobytes(), "service route: records differ"
+        assert d_srec[:D].cpu().numpy().tobytes() == wsrec.tobytes(), "service route: service records differ"
+        assert d_xl[:D].cpu().numpy().tobytes() == wxl.tobytes(), "service route: translation records differ"
+        sec_v = timed(torch, stream, lambda: call(), args.steps, 2)
+        sec_r = timed(torch, stream, lambda: call(d_records=d_rec), args.steps, 2)
+        sec_a = timed(torch, stream, lambda: call(d_records=d_rec, d_svc_records=d_srec, d_xlate=d_xl), args.steps, 2)
+        ran = wsrec["state"] != 0
+        out[name] = {
+            "service_hit_frac": float(np.isin(wxl["status"], (2, 3)).mean()),
+            "translated_frac": float((wxl["status"] == 2).mean()), "no_service_frac": float((wxl["status"] == 3).mean()),
+            "service_state_frac": {k_: float((wsrec["state"][ran] == s_).mean()) if ran.any() else 0.0
+                                   for s_, k_ in ((1, "new"), (3, "reply"), (4, "related"))},
+            "egress_state_frac": {k_: float((wrec["state"][wrec["state"] != 0] == s_).mean())
+                                  for s_, k_ in ((1, "new"), (2, "established"), (3, "reply"), (4, "related"))},
+            "verdicts_only": {"kernel_ms": sec_v * 1e3, "Gframes_s": n / sec_v / 1e9},
+            "with_records": {"kernel_ms": sec_r * 1e3, "Gframes_s": n / sec_r / 1e9,
+                             "over_egress_ct_records_same_run": sec_r / sec_egress_rec},
+            "with_records_svc_records_xlate": {"kernel_ms": sec_a * 1e3, "Gframes_s": n / sec_a / 1e9,
+                                               "over_egress_ct_records_same_run": sec_a / sec_egress_rec}}
+        del d_raw
+    svc.destroy()
+    return out
+
+
 def _bench_l4_frames_egress(torch, dev, stream, cl, args, maps, slots, ipc, s4, s6, tports, D, n, reps, sec_in,
                             sec_in_ct, sec_in_ct_rec):
     """l4_frames_kernel<EgressProg> on an egress batch of the ingress line's shape:
@@ -372,7 +455,8 @@ def _bench_l4_frames_egress(torch, dev, stream, cl, args, maps, slots, ipc, s4, 
     Checked against cg_diag_l4_frames_egress_eval_host over the first copy;
     timed without conntrack and, against a global map derived as
     _bench_l4_frames_ct derives it, with and without records.  The ratios
-    are to the ingress kernels' times of this same run."""
+    are to the ingress kernels' times of this same run.  → (the services
+    object of _bench_l4_frames_services on this batch, the egress object)."""
     from cilium_amd import _native as N
     from cilium_amd import synth
     from cilium_amd.classifier import CT_KEY_DTYPE, FRAME_INFO_DTYPE
@@ -455,9 +539,12 @@ def _bench_l4_frames_egress(torch, dev, stream, cl, args, maps, slots, ipc, s4, 
     sec_ct = timed(torch, stream, lambda: arr.frame_egress_verdicts_dev(d_raw, d_off, n, d_out, conntrack=ct, **kw),
                    args.steps, 2)
     done = wrec["state"] != 0
+    del d_raw
+    svc_res = _bench_l4_frames_services(torch, dev, stream, cl, args, arr, ct, kw, hkw, raw, off, winfo, l4o, d_off,
+                                        d_out, D, n, reps, sec_rec)
     ct.destroy()
     arr.destroy()
-    return {"kernel": "l4_frames_kernel<EgressProg>", "frames": n, "distinct_frames": D, "blob_bytes_per_frame": blob / D,
+    return svc_res, {"kernel": "l4_frames_kernel<EgressProg>", "frames": n, "distinct_frames": D, "blob_bytes_per_frame": blob / D,
             "policy_verdict_frac": float((winfo["t"]["flags"] != 0).mean()), "allowed_frac": float((want >= 0).mean()),
             "source_check_drop_frac": float(np.isin(want, (-130, -131, -132)).mean()),
             "no_conntrack": {"kernel_ms": sec * 1e3, "Gframes_s": n / sec / 1e9, "over_ingress_same_run": sec / sec_in},
@@ -621,8 +708,9 @@ def bench_l4_frames(torch, dev, stream, cl, args, threads):
     dd_o.cpu().numpy()
     wall_f = time.perf_counter() - t0
     del dd, dd_o, d_raw, d_off, d_len, d_out
-    eg_res = _bench_l4_frames_egress(torch, dev, stream, cl, args, maps, slots, ipc, s4, s6, tports, D, n, reps, sec,
-                                     ct_res["kernel_ms"] * 1e-3, ct_res["with_records"]["kernel_ms"] * 1e-3)
+    svc_res, eg_res = _bench_l4_frames_egress(torch, dev, stream, cl, args, maps, slots, ipc, s4, s6, tports, D, n, reps, sec,
+                                              ct_res["kernel_ms"] * 1e-3,
+                                              ct_res["with_records"]["kernel_ms"] * 1e-3)
     per_frame = blob / D + 8 + 4
     return line("L4 verdicts/s from raw frames across 256 endpoints (l4_frames_kernel: header walk, endpoint map, "
                 "ipcache, policy program array)", n, sec, per_frame + 4, "l4_frames_kernel<IngressProg<ep, ipc>>", cpu,
@@ -634,6 +722,7 @@ def bench_l4_frames(torch, dev, stream, cl, args, threads):
                  "algorithmic_bytes_per_frame_in": per_frame,
                  "with_conntrack": ct_res,
                  "egress": eg_res,
+                 "services": svc_res,
                  "tuple_route_ceiling": {"kernel_ms": sec_a * 1e3, "tuples": n_a, "Gtuples_s": n_a / sec_a / 1e9},
                  "from_host_data": {"frames": D, "host_extract_s": t_extract, "tuple_route_wall_s": wall_b,
                                     "frames_wall_s": wall_f, "frames_left_unparsed": int(D - len(plain))}})
